@@ -18,8 +18,15 @@ RCCL (ring), so the per-GPU work is fixed as N grows (weak scaling).  A
 mutation + evaluation included; migrations that fall in the timed window are
 timed too.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--problem P]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--problem P] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (driver, N > 1)
+
+A plain run sets up, warms up, times the K steps and prints the result line;
+nothing else is measured.  ``--dump-outputs DIR`` also writes the population
+the last timed step left (see dump_outputs) so that two builds run with the
+same arguments can be compared output for output: the initial population
+depends on ``--seed`` alone.  ``--full`` is where measurements beyond the
+headline figure belong; there are none so far.
 
 Prints ONE JSON line (rank 0): value = total evals/s over all GPUs.  The line
 also says how the islands migrated (transport, rccl_ranks, timed vs expected
@@ -88,6 +95,45 @@ def expected_migrations(g0: int, steps: int, every: int) -> int:
     return sum(1 for g in range(g0, g0 + steps) if g > 0 and g % every == 0)
 
 
+DUMP_GENOME_BYTES = 32 << 20  # float32 budget of the dumped genome sample (the whole dump stays under 64 MB)
+
+
+def dump_outputs(ga, best: float, out_dir: str, rank: int, world: int) -> None:
+    """What a caller of the timed path holds after its last step, as .npy:
+
+      scores         float32 [pop]      every individual's fitness
+      genomes        float32 [n, L]     decoded genomes of a fixed sample of n rows
+                                        (all of them when the population fits the budget)
+      genomes_index  float64 [n]        the sampled row numbers, ascending
+      best_fitness   float64 [1]        the best score over all islands
+
+    The sample depends on the population size and the genome length alone
+    (its own generator, seed 0), so two builds run with the same arguments
+    dump the same rows.  Ranks > 0 of a multi-GPU run add a ``.rank<r>``
+    suffix to the names."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f".rank{rank}" if world > 1 and rank > 0 else ""
+    scores = ga.scores
+    pop, length = int(scores.numel()), int(ga.problem.length)
+    n = max(1, min(pop, DUMP_GENOME_BYTES // (4 * max(length, 1))))
+    if n < pop:
+        idx = torch.randperm(pop, generator=torch.Generator().manual_seed(0))[:n].sort().values
+    else:
+        idx = torch.arange(pop)
+    rows = ga.rows
+    genomes = ga.problem.decode(rows.index_select(0, idx.to(rows.device)))
+    arrays = {
+        "scores": scores.detach().to("cpu", torch.float32).numpy(),
+        "genomes": genomes.detach().to("cpu", torch.float32).reshape(n, -1).numpy(),
+        "genomes_index": idx.to(torch.float64).numpy(),
+        "best_fitness": np.asarray([best], dtype=np.float64),
+    }
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), arr)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -108,6 +154,12 @@ def main() -> int:
     ap.add_argument("--rccl-self", action="store_true",
                     help="one GPU, no torchrun: the island migrates with itself over a 1-rank RCCL communicator "
                          "(the per-GPU migration cost of an N-GPU run, minus the xGMI wire)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the population the last step left (scores, a fixed sample of "
+                         "decoded genomes, the best fitness) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures beyond its headline figure; the plain run times "
+                         "the headline alone (this benchmark has no such extras so far)")
     a = ap.parse_args()
 
     rank, world, device = init_distributed("gloo" if a.cpu else None)
@@ -162,6 +214,8 @@ def main() -> int:
     evals = gens_per_sec * pop * world
     ref = REFSEM_EVALS_PER_SEC_PER_GPU.get(a.problem.replace("_rot", ""))
     healthy = not any_degraded and max_failures == 0 and max_short <= 0
+    if a.dump_outputs:
+        dump_outputs(ga, best, a.dump_outputs, rank, world)
     if rank == 0:
         xo = ops.get("crossover", ga.operators.crossover)
         out = {

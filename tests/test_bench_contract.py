@@ -47,6 +47,47 @@ def test_expected_migrations():
     assert bench.expected_migrations(5, 500, 0) == 0
 
 
+def _dump(tmp, *extra):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--cpu", "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--dump-outputs", str(tmp), *extra]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(tmp))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes the population the last timed step left: every
+    score, a fixed sample of decoded genomes whose scores the torch oracle
+    reproduces, the best fitness; the same arguments give the same arrays,
+    and --full is accepted."""
+    import numpy as np
+    import torch
+
+    import libpga_amd as pga
+
+    a, b = tmp_path / "a", tmp_path / "b"
+    a.mkdir(), b.mkdir()
+    # 40000 rows of 1024 bits exceed the genome budget: 8192 rows are sampled
+    out = _dump(a, "--pop", "40000")
+    assert out["steps"] == 3 and out["ms_per_step"] > 0
+    _dump(b, "--pop", "40000", "--full")
+    names = sorted(p.name for p in a.iterdir())
+    assert names == ["best_fitness.npy", "genomes.npy", "genomes_index.npy", "scores.npy"]
+    arr = {n[:-4]: np.load(a / n) for n in names}
+    assert sum(v.nbytes for v in arr.values()) <= 64 << 20
+    assert all(v.dtype in (np.float32, np.float64) for v in arr.values())
+    assert arr["scores"].shape == (40000,) and arr["genomes"].shape == (8192, 1024)
+    idx = arr["genomes_index"].astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < 40000
+    ref = pga.models.OneMax(1024).reference_fitness(torch.from_numpy(arr["genomes"]).to(torch.uint8))
+    assert np.array_equal(ref.numpy().astype(np.float32), arr["scores"][idx])
+    assert arr["best_fitness"][0] == arr["scores"].max() == out["best_fitness"]
+    for n in names:
+        assert np.array_equal(np.load(a / n), np.load(b / n)), n
+
+
 def test_bench_tsp256_two_ranks_gloo():
     """BASELINE config 5 through the driver's launcher (reduced population)."""
     out = _run("--steps", "12", "--warmup", "2", "--problem", "tsp256", "--crossover", "pmx", "--pop", "1024")
