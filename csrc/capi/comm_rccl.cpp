@@ -71,7 +71,6 @@ class RcclComm final : public Comm {
   int size() const override { return n_; }
   const char* name() const override { return all_ ? "rccl-all" : "rccl"; }
   bool drives_all_ranks() const override { return all_; }
-  hipStream_t transport_stream(const LocalRank& l) override { return streams_[ensure_stream(l)]; }
 
   void set_fault(int every, int mode) override {
     if (mode != 0 && mode != 3 && mode != 4)

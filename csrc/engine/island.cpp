@@ -54,14 +54,6 @@ Island::Island(const Config& cfg, int device) : cfg_(cfg), device_(device) {
   out_best_ = alloc(64);
   stats_ = alloc(4ull * (4 + 3 * 1024));
   aux_on_ = std::getenv("PGA_TSP_NO_LDS") == nullptr;  // verification: the f32 L2 matrix path
-  persistent_ = [] {
-    const char* e = std::getenv("PGA_TP_MULTI");
-    return e && e[0] == '1';
-  }();
-  if (on_gpu() && cfg_.encoding == ENC_BINARY) {  // binary_gen_tp's pair-pool counters (stamp 0 = stale)
-    tp_pool_ = alloc(tp_pool_bytes(kMaxGrid));
-    PGA_HIP_CHECK(hipMemset(tp_pool_.ptr, 0, tp_pool_.bytes));
-  }
   if (cfg_.encoding == ENC_BINARY) {
     const uint32_t rem = cfg_.L - 128 * (chunks_ - 1);
     uint32_t m[4];
@@ -78,8 +70,8 @@ Island::~Island() {
   Buffer* all[] = {&rows_[0],   &rows_[1],     &scores_[0],   &scores_[1],  &best_[0],  &best_[1],   &mut_thr_,
                    &obj_data_[0], &obj_data_[1], &keys_[0], &keys_[1], &elite_idx_, &cumfit_, &cum_ws_, &roul_guide_, &topk_ws_, &stats_,
                    &out_best_,  &scratch_, &compat_rand_, &ev_parts_, &gen_dev_, &rank_order_, &rank_ws_, &qubo_qt_,
-                   &knap_tab_, &stats_parts_[0], &stats_parts_[1], &hist_, &qk_ws_, &tp_pool_, &obj_aux_,
-                   &fhist_[0], &fhist_[1], &fhist_[2], &multi_bar_};
+                   &knap_tab_, &stats_parts_[0], &stats_parts_[1], &hist_, &qk_ws_, &obj_aux_,
+                   &fhist_[0], &fhist_[1], &fhist_[2]};
   drop_graph();
   if (cap_stream_) (void)hipStreamDestroy(cap_stream_);
   for (Buffer* b : all) {
@@ -183,7 +175,7 @@ void Island::set_operators(const Config& c) {
     cumfit_ = alloc(4ull * (cfg_.S + 4));  // + 4: the GEN kernels' 16-byte window loads (tp.hpp)
     if (on_gpu()) {
       cum_ws_ = alloc(4ull * roulette_workspace_floats(cfg_.S));
-      roul_guide_ = alloc(8ull * (cfg_.S + 4));  // packed: {guide, cumfit} per entry (roul_packed)
+      roul_guide_ = alloc(4ull * (cfg_.S + 1));  // guide[0..S]: roulette_bucket's range
     }
   }
   if (cfg_.selection == SEL_RANK && !rank_order_.ptr) {
@@ -329,7 +321,6 @@ GenArgs Island::make_args(int mode) {
   a.tour_k = cfg_.tour_k;
   a.cumfit = (const float*)cumfit_.ptr;
   a.roul_guide = (const uint32_t*)roul_guide_.ptr;
-  a.roul_packed = roul_guide_.ptr && roul_packed() ? 1u : 0u;
   a.roul_scale = cum_ws_.ptr ? (const float*)cum_ws_.ptr + kRoulScale : nullptr;
   a.rank_order = (const uint32_t*)rank_order_.ptr;
   a.rank_thresh = rank_thresh_of(cfg_.rank_pressure);
@@ -358,20 +349,8 @@ GenArgs Island::make_args(int mode) {
   a.compat_rand = (float*)compat_rand_.ptr;
   a.n_elite = cfg_.n_elite;
   a.elite_idx = cfg_.n_elite > 1 ? (const uint32_t*)elite_idx_.ptr : nullptr;
-  if (mode == MODE_GEN && tp_pool_.ptr && !capturing_) {
-    // a stamp per launch (never 0: zeroed counters are stale); a graph
-    // replay would repeat its stamp, so captured generations run without
-    a.tp_pool = (unsigned long long*)tp_pool_.ptr;
-    if (++tp_seq_ == 0) ++tp_seq_;
-    a.tp_seq = tp_seq_;
-  }
   a.best_cur = (const unsigned long long*)best_[cur_].ptr;
   a.n_best_cur = n_best_[cur_];
-  static const uint32_t nt = [] {
-    const char* e = std::getenv("PGA_TP_NT_STORE");
-    return e && e[0] == '1' ? 1u : 0u;
-  }();
-  a.nt_store = nt;
   a.last_mask = last_mask_;
   if (capturing_) {
     a.gen_dev = (const uint32_t*)gen_dev_.ptr;
@@ -484,14 +463,12 @@ void Island::prepare_generation() {
     const bool one = fused && stats_part_[cur_].grid && integer_objective(cfg_.objective, cfg_.L) &&
                      cfg_.objective != OBJ_KNAPSACK && !roul_fused_off() &&
                      roulette_fused_launch(sc, cfg_.S, (const float*)stats_parts_[cur_].ptr, stats_part_[cur_], cfg_.L,
-                                           (float*)cumfit_.ptr, (uint32_t*)roul_guide_.ptr, (float*)cum_ws_.ptr, stream,
-                                           roul_packed());
+                                           (float*)cumfit_.ptr, (uint32_t*)roul_guide_.ptr, (float*)cum_ws_.ptr, stream);
     if (one) {
     } else if (on_gpu()) {
       roulette_prefix_launch(sc, cfg_.S, fused ? (const float*)stats_parts_[cur_].ptr : nullptr, n_best_[cur_],
                              (float*)cumfit_.ptr, (float*)cum_ws_.ptr, stream, integer_objective(cfg_.objective, cfg_.L));
-      roulette_guide_launch((const float*)cumfit_.ptr, cfg_.S, (uint32_t*)roul_guide_.ptr, (float*)cum_ws_.ptr, stream,
-                            roul_packed());
+      roulette_guide_launch((const float*)cumfit_.ptr, cfg_.S, (uint32_t*)roul_guide_.ptr, (float*)cum_ws_.ptr, stream);
     } else {
       cpu::roulette_prefix(sc, cfg_.S, (float*)cumfit_.ptr);
     }
@@ -528,58 +505,7 @@ void Island::run(uint32_t n) {
     rank_cnt_of_ = -1;                 // (nor rank counts; their sorts overwrite the workspace)
     if (run_graph(reps, fresh)) n -= reps * graph_g_;
   }
-  if (run_multi(n)) return;
   run_plain(n);
-}
-
-bool Island::run_multi(uint32_t n) {
-  // off by default (PGA_TP_MULTI=1 turns it on): measured slower on MI355X,
-  // the barrier's L2 writeback + invalidate and its polling cost more than the
-  // launch ramp it removes (interleaved A/B, profiles/persistent_ab_r06.txt:
-  // 94.7 vs 89.5 us/gen over 500 generations, 97.3 vs 91.7 over 20)
-  if (!persistent_ || n < 2 || !on_gpu() || cfg_.encoding != ENC_BINARY || jit_ || capturing_ || hist_on_) return false;
-  if (!integer_objective(cfg_.objective, cfg_.L) || cfg_.objective == OBJ_KNAPSACK || cfg_.n_elite > 1 ||
-      (cfg_.selection != SEL_TOURNAMENT && cfg_.selection != SEL_RANDOM))
-    return false;  // (no per-generation host work between the generations: prepare_generation is empty)
-  GenArgs a = make_args(MODE_GEN);
-  const int nx = cur_ ^ 1;
-  MultiGenArgs mg;
-  mg.parts[0] = (unsigned long long*)best_[nx].ptr;  // generation i writes the partials of parity cur_ ^ 1 ^ (i & 1)
-  mg.parts[1] = (unsigned long long*)best_[cur_].ptr;
-  mg.stats[0] = a.stats_parts;
-  mg.stats[1] = a.stats_parts ? (float*)stats_parts_[cur_].ptr : nullptr;
-  mg.gens = n;
-  if (!multi_bar_.ptr) multi_bar_ = alloc(256);
-  mg.barrier = (uint32_t*)multi_bar_.ptr;
-  bool fh = fhist_ready_for(a);
-  if (fh) {
-    for (int j = 0; j < 3; ++j) mg.hist[j] = (uint32_t*)fhist_[j].ptr;
-    mg.hist_rot = fhist_rot_ % 3;
-    mg.hist_bins = cfg_.L + 1;
-    mg.hist_zero_words = fused_hist_words(cfg_.L + 1);
-  }
-  TraceRange tr("pga.generations_multi", 2);
-  const uint32_t grid = binary_launch_multi(a, mg, stream);
-  if (grid == 0) return false;
-  rank_cnt_of_ = -1;
-  fh = fh && binary_hist_written();
-  for (uint32_t i = 0; i < n; ++i) {  // the bookkeeping of n plain generations
-    n_best_[cur_ ^ 1] = grid;
-    set_stats_ok(cur_ ^ 1, a.stats_parts != nullptr);
-    if (fh) {
-      const int w = (int)(fhist_rot_ % 3), z = (int)((fhist_rot_ + 1) % 3);
-      ++fhist_rot_;
-      fhist_of_[cur_ ^ 1] = w;
-      fhist_clean_[w] = true;
-      fhist_clean_[z] = true;
-      if (fhist_of_[cur_] == z) fhist_of_[cur_] = -1;
-    } else {
-      fhist_of_[cur_ ^ 1] = -1;
-    }
-    qk_valid_[cur_ ^ 1] = false;
-    swap();
-  }
-  return true;
 }
 
 bool Island::run_tiny(uint32_t n) {
@@ -992,18 +918,6 @@ void Island::immigrate(uint32_t k, const void* in_rows, const float* in_scores) 
 void Island::set_fused_histogram(bool on) {
   fhist_user_ = on;
   fhist_on_ = on || cfg_.n_elite > 1;
-}
-
-bool Island::roul_packed() const {
-  // PGA_ROUL_PACKED=1: the GEN kernel reads one packed {guide, cumfit} table.
-  // Off by default: measured much slower (167.7 vs 130.1 us/gen, OneMax-1024
-  // roulette; profiles/roulette_r06.md): the guide lookups' lines then hold
-  // 16 buckets instead of 32, and the pick's working set doubles
-  static const bool on = [] {
-    const char* e = std::getenv("PGA_ROUL_PACKED");
-    return e && e[0] == '1';
-  }();
-  return on && cfg_.S < (1ull << 28);
 }
 
 bool Island::roul_fused_off() {

@@ -428,7 +428,6 @@ uint32_t JitKernel::gen_launch(hipFunction_t f, const void* args, size_t args_by
   const TpGeom t = tp_geometry_occ(S, 1, occ, 64 / group_size(a.chunks));
   a.tp_unit = t.unit;
   const uint32_t grid = std::min(t.grid, max_grid);
-  a.tp_pool_units = a.tp_pool && grid == t.grid ? tp_pool_units(t, S) : 0u;
   a.tp_skew = grid == t.grid && a.encoding == ENC_BINARY ? tp_skew_units(t, S) : 0u;
   // kernel arguments as one packed buffer: (GenArgs a, unsigned long long* parts)
   std::vector<char> buf(args_bytes + 16);

@@ -414,35 +414,10 @@ __device__ unsigned long long pga_tp_clk[kMaxGrid * 4][8];
 // kTpMaxElite (elites the fast kernel routes through its records),
 // kSegBatches and the work units: tp.hpp
 
-#ifndef PGA_TP_NOKEYS
-#define PGA_TP_NOKEYS 0
-#endif
-// Small tail units (experiment builds: -DPGA_TP_SMALL=1): the last NW
-// units' worth of a 16-wave block's round as 16-child units, so the CU's
-// waves end within one small unit of each other.  Measured slower (round 5,
-// interleaved A/B: 93.4 / 93.5 / 92.7 vs 91.8 / 91.7 / 92.3 us/gen on the
-// driver's early generations, 90.3 vs 89.8 converged): a small unit's
-// RESOLVE (64 lanes of child records for 16 children) and the refill of the
-// PD-deep row pipeline at every unit cost more than the tail they remove.
-#ifndef PGA_TP_SMALL
-#define PGA_TP_SMALL 0
-#endif
-
 __device__ __forceinline__ uint32_t pos16(uint4 r1, uint32_t k) {  // k-th packed 16-bit position
   const uint32_t w = sel4(u32x4{r1.x, r1.y, r1.z, r1.w}, k >> 1);
   return (k & 1u) ? (w >> 16) : (w & 0xFFFFu);
 }
-
-// the uniform-crossover mask of chunk q of child c (ST_XO block q); experiment
-// builds can swap in a multiplicative hash to measure the Philox's share
-#ifdef PGA_TP_XOHASH
-#define PGA_TP_XOMASK(c, q) make_uint4(mut_skip_word((c) * 4u, (q)), mut_skip_word((c) * 4u + 1u, (q)), \
-                                       mut_skip_word((c) * 4u + 2u, (q)), mut_skip_word((c) * 4u + 3u, (q)))
-#else
-#define PGA_TP_XOMASK(c, q) u4(draw<true>(a.key, ST_XO, (c), (q)))
-#endif
-
-typedef uint32_t u32v4 __attribute__((ext_vector_type(4)));
 
 template <int GS, int OBJ, bool FULL, bool DENSE>
 __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long* best_parts) {
@@ -462,7 +437,6 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
   __shared__ unsigned long long lds_red[kTpMaxWaves];
   __shared__ uint32_t lds_next;   // the round's next unbred unit
   __shared__ uint32_t lds_tnext;  // the round's next tournament segment
-  __shared__ uint32_t lds_role;   // the round's producer tickets (tp_producers)
   __shared__ uint32_t lds_ready[kTpMaxSegs];  // per segment: its parents are in LDS
   constexpr bool KMF = OBJ == kObjKnapMfma;
   __shared__ uint4 lds_kscr[KMF ? kTpMaxWaves : 1][kKnapScratch];      // knapsack: per-wave chunk / C scratch
@@ -489,9 +463,6 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
   const bool have = FULL || q < a.chunks, last = q == a.chunks - 1;
   const uint32_t qq = have ? q : 0u;
   const uint32_t clen = have ? chunk_len(L, q) : 0u;
-  const bool tourn = a.selection == SEL_TOURNAMENT;  // tour_k == 2 guaranteed by the launcher
-  const bool rank = a.selection == SEL_RANK;
-  const bool roul = a.selection == SEL_ROULETTE;     // else random
   const bool xo_on = a.crossover != XO_NONE;
   const bool range = a.crossover != XO_UNIFORM;  // ONE/TWO_POINT, or NONE (empty range)
   // DENSE: per-chunk geometric bit-flips; otherwise the record carries the
@@ -508,7 +479,7 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
 
   // this block's children [bbegin, bend) (tp.hpp)
   const uint32_t U = tp_unit(a, NG);  // children per breed unit (tp.hpp)
-  constexpr uint32_t USMALL = PD * NG > 16u ? PD * NG : 16u;  // the round's tail units (a power of two <= 64)
+  const uint32_t nst = U / NG;        // steps of a unit
   uint32_t bbegin, bend;
   tp_block_range(S, U, bbegin, bend, a.tp_skew);
   const uint32_t pcap = tp_par_cap(NW);
@@ -518,17 +489,6 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
   uint32_t* lds_hist = (uint32_t*)(pga_dyn_lds + NW * 4096u + pcap * 8u);  // (never with the JIT staging)
   const bool hist = HISTK && (a.key_hist != nullptr || a.rank_counts != nullptr);  // block-uniform
   const uint32_t hmax = a.hist_bins - 1u;
-  // the pair pool (tp.hpp): one round, tournament or random selection; the
-  // block's own units end at own_end, the last P units are the pair's
-  const uint32_t P = a.tp_pool_units;
-  bool pool_on = a.tp_pool != nullptr && P > 0u && bend - bbegin <= pcap && (tourn || a.selection == SEL_RANDOM);
-  if (pool_on && a.n_elite > 0) {  // elites stay in block 0's own units (their sources are in its LDS)
-    uint32_t b0b, b0e;
-    tp_share(S, U, 0, b0b, b0e, a.tp_skew);
-    pool_on = tp_pool_start(b0b, b0e, U, P) >= a.n_elite;
-  }
-  const uint32_t own_end = pool_on ? tp_pool_start(bbegin, bend, U, P) : bend;
-  const uint32_t pair = blockIdx.x & ~1u, npair = pair + 1u < gridDim.x ? 2u : 1u;
 
   // The elite sources of children [0, n_elite) (n_elite <= kTpMaxElite, for
   // the block that holds any of them) and the mutation table are loaded by
@@ -541,7 +501,7 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
   if (KMF)
     for (uint32_t i = threadIdx.x; i < kKnapSlices * 4 * kKnapMaxCols; i += blockDim.x)
       lds_ktab[i] = ((const uint4*)a.knap_tab)[i];
-  if (threadIdx.x == 0) lds_next = lds_tnext = lds_role = lds_pro = 0;
+  if (threadIdx.x == 0) lds_next = lds_tnext = lds_pro = 0;
   if (threadIdx.x < kTpMaxSegs) lds_ready[threadIdx.x] = 0;
   if (hist) {
     for (uint32_t i = threadIdx.x; i < a.hist_bins; i += blockDim.x) lds_hist[i] = 0;
@@ -549,7 +509,6 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
       for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.hist_zero_words; i += gridDim.x * blockDim.x)
         a.hist_zero[i] = 0;
   }
-  const uint32_t nprod = tp_producers(NW);
 
   unsigned long long my_best = 0;
   ScoreStats st;
@@ -560,14 +519,8 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
   unsigned long long clk_t = 0, clk_b = 0, n_bred = 0, clk_spin = 0;
 #endif
   for (uint32_t rbeg = bbegin; rbeg < bend; rbeg += pcap) {  // block-uniform rounds
-    const uint32_t rend0 = rbeg + pcap < bend ? rbeg + pcap : bend;
-    const uint32_t rend = rend0 < own_end ? rend0 : own_end;                // the round's own children
-    // the round's units: U children each (PGA_TP_SMALL: the last NW units'
-    // worth of a 16-wave block as small units of USMALL >= PD steps)
-    const uint32_t nu = (rend - rbeg + U - 1) / U;
-    const bool tail_small = PGA_TP_SMALL && USMALL < U && NW == kTpMaxWaves && !pool_on && nu >= 2u * NW;
-    const uint32_t nbig = tail_small ? nu - NW : nu;
-    const uint32_t nb = nbig + (tail_small ? (rend - rbeg - nbig * U + USMALL - 1) / USMALL : 0u);
+    const uint32_t rend = rbeg + pcap < bend ? rbeg + pcap : bend;  // the round's children
+    const uint32_t nu = (rend - rbeg + U - 1) / U;                  // its units: U children each
     const uint32_t nseg = (rend - rbeg + kSegBatches * 64 - 1) / (kSegBatches * 64);  // its tournament segments
     __syncthreads();  // tables / counters visible; the previous round's records and parents released
 #ifdef PGA_TP_TIMING
@@ -593,8 +546,7 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
     // segment in flight at once; the contestants wait in the wave's record
     // ring (free until it breeds).  A wave breeds as soon as no segment is
     // left; a unit's RESOLVE waits for its segment's flag (no block barrier)
-    const bool produce = nprod >= NW || tp_ticket(&lds_role, lane) < nprod;  // wave-uniform
-    while (produce) {
+    for (;;) {
       const uint32_t sg = tp_ticket(&lds_tnext, lane);
       if (sg >= nseg) break;
       const uint32_t begin = rbeg + sg * kSegBatches * 64u;
@@ -603,7 +555,7 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
       // the contestants wait in the wave's record ring (4 x 64 x 16 B = its
       // 4 KiB, free until it breeds); every key load of the segment in flight
       // at once (tp.hpp, the one definition shared with real_gen_tp)
-      tp_select_segment<KEY ? (PGA_TP_NOKEYS ? TP_NOKEY : TP_KEY16) : TP_F32>(a, begin, end, lane, &rec[0][0][0], par);
+      tp_select_segment<KEY ? TP_KEY16 : TP_F32>(a, begin, end, lane, &rec[0][0][0], par);
       // publish: the segment's parents (this wave's LDS stores, in order)
       // before its flag
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -637,38 +589,15 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
     }                                                                                                           \
     const uint32_t tc = (US) + lane;                                                                            \
     const uint32_t cc = tc < (UE) ? tc : (UE) - 1;                                                              \
-    uint32_t pa, pb;                                                                                            \
-    if ((US) - rbeg < rend - rbeg) { /* an own unit: parents from the round's tournaments */                    \
-      /* its segment is done (wave-uniform spin, rare) */                                                       \
-      const uint32_t sg_ = ((US) - rbeg) / (kSegBatches * 64u);                                                 \
-      PGA_TP_SPIN0                                                                                              \
-      while (__hip_atomic_load(&lds_ready[sg_], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u)          \
-        __builtin_amdgcn_s_sleep(1);                                                                            \
-      PGA_TP_SPIN1                                                                                              \
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");                                                    \
-      const uint2 pp = lds_par[cc - rbeg];                                                                      \
-      pa = pp.x;                                                                                                \
-      pb = pp.y;                                                                                                \
-    } else { /* a pool unit: its tournaments here, one lane per child (same words) */                           \
-      const u32x4 sb = draw<true>(a.key, ST_SEL, cc, 0);                                                        \
-      const uint32_t i0 = word_to_index(sb.x, S), i1 = word_to_index(sb.y, S);                                  \
-      const uint32_t i2 = word_to_index(sb.z, S), i3 = word_to_index(sb.w, S);                                  \
-      pa = i0;                                                                                                  \
-      pb = i1;                                                                                                  \
-      if (tourn) {                                                                                              \
-        if constexpr (KEY) {                                                                                    \
-          const uint32_t q0 = ELEM(const uint16_t, a.key_cur, i0), q1 = ELEM(const uint16_t, a.key_cur, i1);    \
-          const uint32_t q2 = ELEM(const uint16_t, a.key_cur, i2), q3 = ELEM(const uint16_t, a.key_cur, i3);    \
-          pa = q0 < q1 ? i1 : i0;                                                                               \
-          pb = q2 < q3 ? i3 : i2;                                                                               \
-        } else {                                                                                                \
-          const float f0 = ELEM(const float, a.score_cur, i0), f1 = ELEM(const float, a.score_cur, i1);         \
-          const float f2 = ELEM(const float, a.score_cur, i2), f3 = ELEM(const float, a.score_cur, i3);         \
-          pa = f0 < f1 ? i1 : i0;                                                                               \
-          pb = f2 < f3 ? i3 : i2;                                                                               \
-        }                                                                                                       \
-      }                                                                                                         \
-    }                                                                                                           \
+    /* its segment is done (wave-uniform spin, rare) */                                                         \
+    const uint32_t sg_ = ((US) - rbeg) / (kSegBatches * 64u);                                                   \
+    PGA_TP_SPIN0                                                                                                \
+    while (__hip_atomic_load(&lds_ready[sg_], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u)            \
+      __builtin_amdgcn_s_sleep(1);                                                                              \
+    PGA_TP_SPIN1                                                                                                \
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");                                                      \
+    const uint2 pp = lds_par[cc - rbeg]; /* parents from the round's tournaments */                             \
+    uint32_t pa = pp.x, pb = pp.y;                                                                              \
     const u32x4 misc = bin_misc<true>(a.key, cc);                                                               \
     const bool elite = tc < a.n_elite;                                                                          \
     const bool xo = !elite && xo_on && do_crossover(a, misc.x);                                                 \
@@ -724,57 +653,32 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
     // hipcc assumes the fewest outstanding loads over all paths, so a
     // conditionally issued load would make the next wait drain it): an
     // exhausted load cursor re-reads the breed cursor's rows.
-    // NEXT unit [US, UE) of this wave (US = kNoUnit: none): the block's own
-    // units from its LDS counter, then pool units from the pair's counter
+    // NEXT unit [US, UE) of this wave (US = kNoUnit: none), from the block's
+    // LDS counter
     constexpr uint32_t kNoUnit = 0xFFFFFFFFu;
-    bool steal = false;  // wave-uniform: own units exhausted, pulling pool units
-#define PGA_TP_NEXT(US, UE, UN)                                                                             \
+#define PGA_TP_NEXT(US, UE)                                                                                 \
   {                                                                                                         \
     US = kNoUnit;                                                                                           \
-    UN = U / NG;                                                                                            \
-    if (!steal) {                                                                                           \
-      const uint32_t tk_ = tp_ticket(&lds_next, lane);                                                      \
-      if (tk_ < nbig) {                                                                                     \
-        US = rbeg + tk_ * U;                                                                                \
-        UE = US + U < rend ? US + U : rend;                                                                 \
-      } else if (tk_ < nb) { /* a small tail unit */                                                        \
-        US = rbeg + nbig * U + (tk_ - nbig) * USMALL;                                                       \
-        UE = US + USMALL < rend ? US + USMALL : rend;                                                       \
-        UN = USMALL / NG;                                                                                   \
-      } else {                                                                                              \
-        steal = pool_on;                                                                                    \
-      }                                                                                                     \
-    }                                                                                                       \
-    while (steal && US == kNoUnit) { /* ticket t: block pair + t % npair, its pool unit t / npair */       \
-      const uint32_t t_ = tp_pool_grab(a.tp_pool + (pair >> 1) * kTpPoolStride, a.tp_seq, lane);            \
-      if (t_ / npair >= P) {                                                                                \
-        steal = false;                                                                                      \
-      } else {                                                                                              \
-        uint32_t pb_, pe_;                                                                                  \
-        tp_share(S, U, pair + t_ % npair, pb_, pe_, a.tp_skew);                                             \
-        const uint32_t ps_ = tp_pool_start(pb_, pe_, U, P) + (t_ / npair) * U;                             \
-        if (ps_ < pe_) {                                                                                    \
-          US = ps_;                                                                                         \
-          UE = ps_ + U < pe_ ? ps_ + U : pe_;                                                               \
-        }                                                                                                   \
-      }                                                                                                     \
+    const uint32_t tk_ = tp_ticket(&lds_next, lane);                                                        \
+    if (tk_ < nu) {                                                                                         \
+      US = rbeg + tk_ * U;                                                                                  \
+      UE = US + U < rend ? US + U : rend;                                                                   \
     }                                                                                                       \
   }
 
-    uint32_t ns, ne = 0, nn = 0;  // the wave's next unit and its steps (prefetched ticket)
-    PGA_TP_NEXT(ns, ne, nn)
+    uint32_t ns, ne = 0;  // the wave's next unit (prefetched ticket)
+    PGA_TP_NEXT(ns, ne)
     if (ns != kNoUnit) {
-      // breed cursor: ring slot, step, its unit [bs, be) and steps.  Every
-      // unit takes its full size / NG steps, a partial one (only ever at S)
+      // breed cursor: ring slot, step and its unit [bs, be).  Every unit
+      // takes its full nst = U / NG steps, a partial one (only ever at S)
       // too: its children past S write the padding rows, and a unit never
       // holds fewer steps than the PD the load cursor runs ahead
-      uint32_t nst = nn;
       uint32_t slot = 0, i = 0, bs = ns, be = ne;
-      PGA_TP_NEXT(ns, ne, nn)
+      PGA_TP_NEXT(ns, ne)
       PGA_TP_RESOLVE(bs, be, 0u)
       // load cursor; lpend: at the end of its unit with unit ns next;
       // lmore = false: past the wave's last step
-      uint32_t lslot = 0, li = 0, lbs = bs, lbe = be, lnst = nst;
+      uint32_t lslot = 0, li = 0, lbs = bs, lbe = be;
       bool lpend = false, lmore = true, done = false;
 
       // LOAD the parent rows of the load cursor's step into (YA, YB) and
@@ -787,14 +691,13 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
       li = 0;                                                                                               \
       lbs = ns;                                                                                             \
       lbe = ne;                                                                                             \
-      lnst = nn;                                                                                            \
       lpend = false;                                                                                        \
-      PGA_TP_NEXT(ns, ne, nn)                                                                               \
+      PGA_TP_NEXT(ns, ne)                                                                                   \
     }                                                                                                       \
     const uint4 r = rec[lmore ? lslot : slot][(lmore ? li : i) * NG + g][0];                                \
     YA = ROW(cur, r.x, qq);                                                                                 \
     YB = ROW(cur, r.y, qq);                                                                                 \
-    if (lmore && ++li == lnst) {                                                                            \
+    if (lmore && ++li == nst) {                                                                             \
       lpend = ns != kNoUnit;                                                                                \
       lmore = lpend;                                                                                        \
     }                                                                                                       \
@@ -809,7 +712,7 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
     const uint32_t c = bs + i * NG + g;                                                                     \
     const uint4 r0 = rec[slot][i * NG + g][0];                                                              \
     const uint32_t meta = r0.w;                                                                             \
-    const uint4 m = range ? range_keep_a(q, r0.z & 0xFFFFu, r0.z >> 16) : PGA_TP_XOMASK(c, q);               \
+    const uint4 m = range ? range_keep_a(q, r0.z & 0xFFFFu, r0.z >> 16) : u4(draw<true>(a.key, ST_XO, c, q)); \
     uint4 v = mix4(XA, XB, m);                                                                              \
     if (last) v = and4(v, lmask);                                                                           \
     uint4 fm = make_uint4(0, 0, 0, 0);                                                                      \
@@ -845,12 +748,7 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
       if (have) acc.add(a, v, q);                                                                           \
       sc = acc.template finish<GS>(a);                                                                      \
     }                                                                                                       \
-    if (have) {                                                                                             \
-      if (a.nt_store) /* block-uniform */                                                                   \
-        __builtin_nontemporal_store(__builtin_bit_cast(u32v4, v), (u32v4*)&ROW(nxt, c, q));                 \
-      else                                                                                                  \
-        ROW(nxt, c, q) = v;                                                                                 \
-    }                                                                                                       \
+    if (have) ROW(nxt, c, q) = v;                                                                           \
     if constexpr (JIT) {                                                                                    \
       lds_stage[(i % kJitStageSteps) * 64u + lane] = v;                                                     \
       if (i % kJitStageSteps == kJitStageSteps - 1u || i + 1u == nst) PGA_TP_JIT_EVAL                       \
@@ -876,7 +774,6 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
         i = 0;                                                                                              \
         bs = lbs;                                                                                           \
         be = lbe;                                                                                           \
-        nst = lnst;                                                                                         \
       }                                                                                                     \
     }                                                                                                       \
   }
@@ -956,7 +853,7 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
     clk_b += clock64() - clkB;
 #endif
     __syncthreads();  // every wave out of the round's counters before they are reset
-    if (threadIdx.x == 0) lds_next = lds_tnext = lds_role = 0;
+    if (threadIdx.x == 0) lds_next = lds_tnext = 0;
     if (threadIdx.x < kTpMaxSegs) lds_ready[threadIdx.x] = 0;
   }
 #undef ROW
@@ -993,77 +890,6 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
 template <int GS, int OBJ, bool FULL, bool DENSE>
 __global__ __launch_bounds__(kTpMaxWaves * 64) void binary_gen_tp(GenArgs a, unsigned long long* best_parts) {
   binary_gen_tp_body<GS, OBJ, FULL, DENSE>(a, best_parts);
-}
-
-// ---------------------------------------------------------------------------
-// Persistent multi-generation launch (the headline geometry only: one
-// 16-wave block per CU, every block resident at once): G generations of the
-// same island in ONE launch, a device-wide barrier between them in place of
-// the kernel boundary, so the next generation's blocks start together the
-// moment the barrier drops instead of re-entering one by one through the
-// dispatcher (the launch ramp: the last of 4096 waves started 3.4-4 us after
-// the first, pmc_r05.md).  The barrier does what the kernel boundary did for
-// memory: every block's stores leave its XCD's L2 (agent-scope release) before
-// it arrives, and every block drops stale L2 lines (agent-scope acquire) once
-// all have arrived; the next generation reads the population just written.
-// Integer objectives with tournament / random selection, elitism <= 1, no
-// fused histogram (the launcher checks).  Generation i writes parts[i & 1] and
-// stats[i & 1], so the host's parity bookkeeping is that of G plain launches.
-// ---------------------------------------------------------------------------
-struct GenMulti {
-  GenArgs a;                     // generation 0
-  unsigned long long* parts[2];  // best partials written by even / odd generations
-  float* stats[2];               // {min, sum} partials likewise (nullptr: none)
-  uint32_t gens;
-  uint32_t* bar;  // arrival counter, zero at launch; generation i's barrier waits for grid * (i + 1)
-  uint32_t* hist[3];  // fused key histograms, rotated as Island::run_plain does (hist[0] nullptr: off)
-  uint32_t hist_rot;
-};
-
-__device__ __forceinline__ void tp_grid_sync(uint32_t* bar, uint32_t target) {
-  __syncthreads();  // every wave's stores of the generation are in the L2 (workgroup release)
-  if (threadIdx.x < 64u) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // ... and out of this XCD's L2
-    if (threadIdx.x == 0) {
-      __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      // bounded: a grid that is not co-resident (never expected: the launcher
-      // takes one block per CU) would otherwise hang the device
-      for (uint32_t spins = 0; spins < (1u << 24); ++spins) {
-        if (__hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= target) break;
-        __builtin_amdgcn_s_sleep(1);
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // no stale line of the new population survives
-  }
-  __syncthreads();
-}
-
-template <int GS, int OBJ, bool FULL, bool DENSE>
-__global__ __launch_bounds__(kTpMaxWaves * 64) void binary_gen_tp_multi(GenMulti m) {
-  GenArgs a = m.a;
-  for (uint32_t i = 0;; ++i) {
-    a.stats_parts = m.stats[i & 1u];
-    if (m.hist[0]) {
-      a.key_hist = m.hist[(m.hist_rot + i) % 3u];
-      a.hist_zero = m.hist[(m.hist_rot + i + 1u) % 3u];
-    }
-    binary_gen_tp_body<GS, OBJ, FULL, DENSE>(a, m.parts[i & 1u]);
-    if (i + 1u >= m.gens) break;
-    tp_grid_sync(m.bar, gridDim.x * (i + 1u));
-    // the population just written is the next generation's current one
-    const void* c = a.cur;
-    a.cur = a.next;
-    a.next = const_cast<void*>(c);
-    const float* sc = a.score_cur;
-    a.score_cur = a.score_next;
-    a.score_next = const_cast<float*>(sc);
-    const uint16_t* kc = a.key_cur;
-    a.key_cur = a.key_next;
-    a.key_next = const_cast<uint16_t*>(kc);
-    a.best_cur = m.parts[i & 1u];
-    a.n_best_cur = gridDim.x;
-    ++a.key.gen;
-  }
 }
 
 // ---------------------------------------------------------------------------

@@ -354,11 +354,6 @@ struct GenArgs {
   // two-phase kernels (tp.hpp): children per dynamically assigned breed unit,
   // a power of two in [64 / GS, 64] set by the launcher (0 = 64)
   uint32_t tp_unit;
-  // pair pool of binary_gen_tp (tp.hpp): per block pair one 64-bit counter
-  // (kTpPoolStride apart), this launch's stamp, the units per block in the
-  // pool (0 / nullptr: no pool)
-  unsigned long long* tp_pool;
-  uint32_t tp_seq, tp_pool_units;
   // share skew of binary_gen_tp (tp.hpp tp_share): units each odd block of a
   // pair hands to its even neighbour (0: equal shares)
   uint32_t tp_skew;
@@ -378,9 +373,6 @@ struct GenArgs {
   uint32_t* key_hist;
   uint32_t* hist_zero;
   uint32_t hist_bins, hist_zero_words;
-  // binary_gen_tp: child rows stored non-temporally (experiment knob,
-  // PGA_TP_NT_STORE=1; 0: ordinary stores)
-  uint32_t nt_store;
   // rank selection (binary_gen_tp, integer objectives): when set, every block
   // also stores its LDS key histogram, all hist_bins bins, to
   // rank_counts[bin * gridDim.x + blockIdx.x]: the tile counts of the next
@@ -388,10 +380,6 @@ struct GenArgs {
   // pass then reads nothing.  The launcher sets it only when each block's
   // children are exactly one kRankTile sort tile.
   uint32_t* rank_counts;
-  // roulette, two-phase kernels: roul_guide is the PACKED table, entry e =
-  // {guide[e], cumfit[e] bits} (8 bytes), so a pick's cumfit window usually
-  // sits in the guide line it just fetched (util.hip roulette_*_launch)
-  uint32_t roul_packed;
 };
 // the fused histogram's LDS bins (binary_gen_tp): objectives with more key
 // values use the separate histogram pass

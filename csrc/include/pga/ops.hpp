@@ -55,13 +55,8 @@ TpGeom tp_geometry_occ(uint64_t S, uint32_t islands, uint32_t occ4, uint32_t ng,
 uint32_t tp_dyn_lds_bytes(uint32_t nw, uint32_t pseg = 7);
 // LDS a fused BINARY JIT launch adds for its staged children (tp.hpp kJitStageSteps)
 uint32_t tp_jit_stage_bytes(uint32_t nw);
-// units per block in binary_gen_tp's pair pool for this geometry (tp.hpp;
-// PGA_TP_POOL=d: 1/d of a 16-wave block's units; default 0: off)
-uint32_t tp_pool_units(const TpGeom& t, uint64_t S);
 // share skew for this geometry (tp.hpp tp_share; PGA_TP_SKEW units, default 2)
 uint32_t tp_skew_units(const TpGeom& t, uint64_t S);
-// bytes of pair-pool counters a launch of up to `grid` blocks needs
-inline size_t tp_pool_bytes(uint32_t grid) { return (size_t)(grid + 1) / 2 * 128; }
 int device_cu_count();
 // raise a kernel's dynamic-LDS limit to what its static LDS leaves of the
 // CU's 160 KiB on the current device (once per kernel and device; cheap to
@@ -77,25 +72,6 @@ uint32_t binary_launch(int mode, const GenArgs& a, unsigned long long* best_part
 // binary_launch for one group size GS (binary_gs.hip, one translation unit per GS)
 template <int GS>
 uint32_t binary_launch_group(int mode, const GenArgs& a, unsigned long long* best_parts, hipStream_t s);
-// Persistent multi-generation launch of the headline kernel
-// (binary_dev.hpp binary_gen_tp_multi): `gens` generations from `a`
-// (generation 0), generation i writing best / stats partials parts[i & 1] /
-// stats[i & 1]; barrier: 4 device bytes (zeroed by the launch).  Returns the
-// grid (every generation's partial count) or 0 when the arguments do not
-// qualify (nothing launched: run plain launches).
-struct MultiGenArgs {
-  unsigned long long* parts[2];
-  float* stats[2];
-  uint32_t gens;
-  uint32_t* barrier;
-  // fused key histogram (GenArgs::key_hist) rotation: generation i writes
-  // hist[(rot + i) % 3] and zeroes hist[(rot + i + 1) % 3] (hist[0] nullptr: off)
-  uint32_t* hist[3] = {nullptr, nullptr, nullptr};
-  uint32_t hist_rot = 0, hist_bins = 0, hist_zero_words = 0;
-};
-uint32_t binary_launch_multi(const GenArgs& a, const MultiGenArgs& mg, hipStream_t s);
-template <int GS>
-uint32_t binary_launch_multi_group(const GenArgs& a, const MultiGenArgs& mg, hipStream_t s);
 // whether the last binary_launch on this host thread handed GenArgs::key_hist
 // to its kernel (so the fused key histogram was written and hist_zero
 // cleared); the island marks a histogram valid only on this report
@@ -211,10 +187,7 @@ size_t roulette_workspace_floats(uint64_t S);
 // exact prefix rounded once per entry
 void roulette_prefix_launch(const float* scores, uint64_t S, const float* parts, uint32_t nparts, float* cumfit,
                             float* workspace, hipStream_t s, bool integer = false);
-// packed: guide is the packed table of GenArgs::roul_packed (8 bytes per
-// entry, S + 4 entries; S < 2^28)
-void roulette_guide_launch(const float* cumfit, uint64_t S, uint32_t* guide, float* workspace, hipStream_t s,
-                           bool packed = false);
+void roulette_guide_launch(const float* cumfit, uint64_t S, uint32_t* guide, float* workspace, hipStream_t s);
 // Both in ONE launch for an integer objective whose current population came
 // from binary_gen_tp with partition `part`: its {min, sum} partials (parts,
 // part.grid blocks) give every block its carry, so no pass precedes the scan.
@@ -222,8 +195,7 @@ void roulette_guide_launch(const float* cumfit, uint64_t S, uint32_t* guide, flo
 // rounded to f32 once).  max_score: the objective's largest score; returns
 // false (nothing launched) when a partial sum could be inexact in f32.
 bool roulette_fused_launch(const float* scores, uint64_t S, const float* parts, const TpPartition& part,
-                           uint32_t max_score, float* cumfit, uint32_t* guide, float* workspace, hipStream_t s,
-                           bool packed = false);
+                           uint32_t max_score, float* cumfit, uint32_t* guide, float* workspace, hipStream_t s);
 // stable LSD radix sort (sort.hip: reduce-then-scan, digits of up to 8 bits,
 // count / scan / scatter launches per pass): (keys, vals) by the low `bits`
 // bits of the keys, ascending, or descending (all 32 bits; equal keys keep

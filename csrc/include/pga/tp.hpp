@@ -12,9 +12,6 @@
 
 #include "pga/device.hpp"
 
-#ifndef PGA_TP_NOSCORES
-#define PGA_TP_NOSCORES 0
-#endif
 // batches (x 64 children) per tournament segment
 #ifndef PGA_TP_SEG
 #define PGA_TP_SEG 4
@@ -40,8 +37,7 @@ __device__ __forceinline__ T ld32(const void* base, uint32_t i) {
 // Tournament key modes: the f32 scores; the u16 keys of an integer
 // objective (exact); or quantized u16 keys of a float objective (core.hpp
 // qkey: equal keys fall back to the f32 scores, the exact result either way)
-// (TP_NOKEY: experiment builds only, tournaments on fake keys without loads)
-enum TpKeys : int { TP_F32 = 0, TP_KEY16 = 1, TP_QKEY16 = 2, TP_NOKEY = 3 };
+enum TpKeys : int { TP_F32 = 0, TP_KEY16 = 1, TP_QKEY16 = 2 };
 
 // Parents (A, B) of children [begin + 64 B + lane] for the segment's batches
 // B < kSegBatches -> par[B * 64 + lane].  ixs: 4 x 64 uint4 of LDS scratch
@@ -79,21 +75,11 @@ __device__ __forceinline__ void tp_select_segment(const GenArgs& a, uint32_t beg
       const uint32_t rb = rank_pick(blk.w, b1.x, b1.y, S, a.rank_thresh);
       k0[B] = __builtin_bit_cast(KT, ld32<uint32_t>(a.rank_order, ra));
       k1[B] = __builtin_bit_cast(KT, ld32<uint32_t>(a.rank_order, rb));
-    } else if constexpr (KM == TP_NOKEY) {
-      k0[B] = j.x & 1023u;
-      k1[B] = j.y & 1023u;
-      k2[B] = j.z & 1023u;
-      k3[B] = j.w & 1023u;
     } else if constexpr (KEY) {
       k0[B] = ld32<uint16_t>(a.key_cur, j.x);
       k1[B] = ld32<uint16_t>(a.key_cur, j.y);
       k2[B] = ld32<uint16_t>(a.key_cur, j.z);
       k3[B] = ld32<uint16_t>(a.key_cur, j.w);
-    } else if constexpr (PGA_TP_NOSCORES) {  // experiment builds: tournaments without score loads
-      k0[B] = (float)(j.x & 1023u);
-      k1[B] = (float)(j.y & 1023u);
-      k2[B] = (float)(j.z & 1023u);
-      k3[B] = (float)(j.w & 1023u);
     } else {
       k0[B] = ld32<float>(a.score_cur, j.x);
       k1[B] = ld32<float>(a.score_cur, j.y);
@@ -110,14 +96,13 @@ __device__ __forceinline__ void tp_select_segment(const GenArgs& a, uint32_t beg
     constexpr uint32_t NS = 2 * kSegBatches;
     const float total = a.cumfit[S - 1];
     const float scale = *a.roul_scale;
-    const uint32_t gsh = a.roul_packed ? 1u : 0u;  // packed: entry e = {guide[e], cumfit[e]}
     uint32_t ix[NS];
     float tg[NS];
     #pragma unroll
     for (uint32_t i = 0; i < NS; ++i) {
       const uint32_t w = __builtin_bit_cast(uint32_t, (i & 1u) ? k1[i >> 1] : k0[i >> 1]);
       tg[i] = word_to_unit(w) * total;
-      ix[i] = total > 0.f ? ld32<uint32_t>(a.roul_guide, roulette_bucket(tg[i], scale, S) << gsh) : word_to_index(w, S);
+      ix[i] = total > 0.f ? ld32<uint32_t>(a.roul_guide, roulette_bucket(tg[i], scale, S)) : word_to_index(w, S);
     }
     // kGuideCovered (S < 2^31): the bucket is not the last of its
     // individual's buckets, so that individual's cumfit is above every target
@@ -137,16 +122,7 @@ __device__ __forceinline__ void tp_select_segment(const GenArgs& a, uint32_t beg
     for (uint32_t i = 0; i < NS; ++i) {
       const uint32_t b = ix[i] & ~3u, off = ix[i] - b;
       float4 w = make_float4(tg[i], tg[i], tg[i], tg[i]);  // (covered: no entry below the target)
-      if (!covered[i]) {
-        if (gsh) {  // entries b .. b + 3: 32 bytes of the packed table
-          const uint4 q0 = *(const uint4*)((const char*)a.roul_guide + b * 8u);
-          const uint4 q1 = *(const uint4*)((const char*)a.roul_guide + b * 8u + 16u);
-          w = make_float4(__builtin_bit_cast(float, q0.y), __builtin_bit_cast(float, q0.w),
-                          __builtin_bit_cast(float, q1.y), __builtin_bit_cast(float, q1.w));
-        } else {
-          w = *(const float4*)((const char*)a.cumfit + b * 4u);
-        }
-      }
+      if (!covered[i]) w = *(const float4*)((const char*)a.cumfit + b * 4u);
       // step over the window entries below the target, in order (the padding
       // past cumfit[S - 1] = total is never reached: total >= every target)
       uint32_t p = off;
@@ -167,7 +143,7 @@ __device__ __forceinline__ void tp_select_segment(const GenArgs& a, uint32_t beg
       for (uint32_t i = 0; i < NS; ++i) {
         const bool adv = total > 0.f && v[i] < tg[i];
         ix[i] += adv ? 1u : 0u;
-        v[i] = gsh ? ld32<float>(a.roul_guide, (ix[i] << 1) + 1u) : ld32<float>(a.cumfit, ix[i]);
+        v[i] = ld32<float>(a.cumfit, ix[i]);
       }
     }
     #pragma unroll
@@ -247,22 +223,6 @@ __host__ __device__ inline uint32_t tp_unit(const GenArgs& a, uint32_t NG) {  //
   return u >= lo && u <= 64u && (u & (u - 1u)) == 0u ? u : 64u;
 }
 
-// PRODUCER waves (one 16-wave block per CU): only the first nprod waves of a
-// round run its tournament segments, the others breed from the start, each
-// unit waiting for its segment's flag.  With every wave producing, the whole
-// GPU runs its L2-bound random key reads first (~14 us at the headline, no
-// row traffic) and its HBM-bound row gathers after (phase clocks, round 4);
-// a few producers keep ahead of the breeders (a segment of 256 children per
-// ~1.5 us of key latency against ~70 children per us consumed by a CU) and
-// the two kinds of traffic overlap.  The key reads stay concentrated in the
-// first ~20 us of the kernel, so the 2 MiB key array stays L2-resident.
-#ifndef PGA_TP_PROD
-#define PGA_TP_PROD 0
-#endif
-__device__ __forceinline__ uint32_t tp_producers(uint32_t nw) {
-  return PGA_TP_PROD > 0 && nw == kTpMaxWaves ? (uint32_t)PGA_TP_PROD : nw;
-}
-
 // One ticket per wave from an LDS counter, with no lane divergence: every
 // lane of the (full, converged) wave adds one — the atomic optimizer folds
 // the uniform add into ONE ds_add of 64 and hands the first lane the old
@@ -293,9 +253,6 @@ __device__ __forceinline__ void tp_share(uint32_t S, uint32_t U, uint32_t blk, u
                                          uint32_t skew = 0) {
   uint64_t per = (S + (uint64_t)gridDim.x - 1) / gridDim.x;
   per = (per + U - 1) / U * U;
-#ifdef PGA_TP_SWAPSHARE  // experiment builds: neighbouring blocks (XCDs) trade shares
-  blk = (blk ^ 1u) < gridDim.x ? (blk ^ 1u) : blk;
-#endif
   const uint64_t d = (uint64_t)skew * U < per && (blk | 1u) < gridDim.x ? (uint64_t)skew * U : 0;
   const uint64_t b = (uint64_t)blk * per + ((blk & 1u) ? d : 0), n = (blk & 1u) ? per - d : per + d;
   bb = (uint32_t)(b < S ? b : S);
@@ -304,52 +261,6 @@ __device__ __forceinline__ void tp_share(uint32_t S, uint32_t U, uint32_t blk, u
 __device__ __forceinline__ void tp_block_range(uint32_t S, uint32_t U, uint32_t& bbegin, uint32_t& bend,
                                                uint32_t skew = 0) {
   tp_share(S, U, blockIdx.x, bbegin, bend, skew);
-}
-
-// Pair pool (cross-XCD tail sharing; OFF by default, PGA_TP_POOL=d enables
-// 1/d of each block's units): the last P units of each block's share
-// are bred by whichever wave of the block PAIR (2p, 2p+1: neighbouring blocks
-// land on different XCDs) asks first, through one device-scope counter per
-// pair (GenArgs::tp_pool, 128 B apart).  The XCDs do not finish alike: the
-// phase clocks put the odd XCDs' blocks ~6 us behind the even ones' on every
-// box (round 4), which per-CU counters cannot see.  A counter is 64 bits:
-// the launch stamp (GenArgs::tp_seq, unique per launch) above the ticket
-// count, so no launch has to clear it: a grab that reads an older stamp
-// swaps in (stamp, 1) by compare-exchange (ticket 0); one that reads the
-// current stamp takes a ticket with fetch-add.  Lock-free: every failed
-// exchange means another wave's succeeded (a stale counter is never
-// incremented, so the exchange cannot be starved by concurrent adds), and
-// once the stamp is current it stays so for the launch.  Vector atomics from
-// one lane (never the scalar cache).  Measured (round 4, interleaved A/B):
-// 1/8 pooled 94.3 us/gen vs 89.8 without — a stolen unit runs its own
-// tournaments and refills the row pipeline, which costs more than the XCD
-// skew it removes, so the launcher leaves it off.
-constexpr uint32_t kTpPoolStride = 16;  // u64 per pair counter (128 B)
-// first child of the pool part of share [bb, be): its last min(P, units)
-// whole units (the own part ends on a unit boundary)
-__device__ __forceinline__ uint32_t tp_pool_start(uint32_t bb, uint32_t be, uint32_t U, uint32_t P) {
-  const uint32_t nu = (be - bb + U - 1) / U;
-  return bb + (nu > P ? nu - P : 0u) * U;
-}
-__device__ __forceinline__ uint32_t tp_pool_grab(unsigned long long* ctr, uint32_t seq, uint32_t lane) {
-  uint32_t t = 0;
-  if (lane == 0) {
-    const unsigned long long stamp = (unsigned long long)seq << 32;
-    unsigned long long v = __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (;;) {
-      if ((v >> 32) == (unsigned long long)seq) {
-        t = (uint32_t)__hip_atomic_fetch_add(ctr, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        break;
-      }
-      // a stale stamp: claim ticket 0 of this launch (a failure reloads v)
-      if (__hip_atomic_compare_exchange_strong(ctr, &v, stamp | 1ull, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_AGENT)) {
-        t = 0;
-        break;
-      }
-    }
-  }
-  return __builtin_amdgcn_readfirstlane(t);
 }
 
 }  // namespace dev

@@ -33,7 +33,6 @@ uint32_t go_tp(K kernel, const GenArgs& a0, unsigned long long* parts, hipStream
   const TpGeom t = tp_geometry(a0.S, 1, (const void*)kernel, 64 / group_size(a0.chunks));
   GenArgs a = a0;
   a.tp_unit = t.unit;
-  a.tp_pool_units = a.tp_pool ? tp_pool_units(t, a.S) : 0u;
   a.tp_skew = tp_skew_units(t, a.S);
   // the fused key histogram's LDS bins follow the round's parents
   // (binary_gen_tp's HISTK: the objectives with exact u16 keys)
@@ -43,73 +42,18 @@ uint32_t go_tp(K kernel, const GenArgs& a0, unsigned long long* parts, hipStream
   if (!hist) a.key_hist = nullptr;
   // the rank sort's tile counts: only when block b's children are exactly
   // sort tile b (tp_share with a share of kRankTile, a multiple of every
-  // unit; no pair pool).  The share skew (PGA_TP_SKEW, worth ~0.5 us at the
+  // unit).  The share skew (PGA_TP_SKEW, worth ~0.5 us at the
   // headline) is dropped for it: the count pass it saves costs ~6 us.
   const bool rk = key_obj && a.key_cur != nullptr && a.rank_counts != nullptr && a.hist_bins > 0 &&
-                  a.hist_bins <= kHistMaxBins && a.tp_pool_units == 0 &&
+                  a.hist_bins <= kHistMaxBins &&
                   (a.S + t.grid - 1) / t.grid == kRankTile && (uint64_t)t.grid == (a.S + kRankTile - 1) / kRankTile;
   if (rk) a.tp_skew = 0;
   else a.rank_counts = nullptr;
   hipLaunchKernelGGL(kernel, t.grid, t.block, t.lds + (hist || rk ? 4u * a.hist_bins : 0u), s, a, parts);
   binary_hist_written() = hist;
   binary_rank_counts_written() = rk;
-  if (a.tp_pool_units == 0) binary_tp_partition() = TpPartition{t.grid, tp_unit(a, 64u / group_size(a.chunks)), a.tp_skew};
+  binary_tp_partition() = TpPartition{t.grid, tp_unit(a, 64u / group_size(a.chunks)), a.tp_skew};
   return t.grid;
-}
-
-// G generations in one persistent launch (binary_dev.hpp binary_gen_tp_multi):
-// only the headline geometry (one 16-wave block per CU), else 0 (run them
-// one launch each)
-template <typename K>
-uint32_t go_tp_multi(K kernel, const GenArgs& a0, const MultiGenArgs& mg, hipStream_t s) {
-  const TpGeom t = tp_geometry(a0.S, 1, (const void*)kernel, 64 / group_size(a0.chunks));
-  if (t.block != kTpMaxWaves * 64 || t.grid > (uint32_t)device_cu_count()) return 0;
-  GenMulti m;
-  m.a = a0;
-  m.a.tp_unit = t.unit;
-  m.a.tp_pool = nullptr;
-  m.a.tp_pool_units = 0;
-  m.a.tp_skew = tp_skew_units(t, a0.S);
-  const bool hist = mg.hist[0] && mg.hist[1] && mg.hist[2] && mg.hist_bins > 0 && mg.hist_bins <= kHistMaxBins;
-  m.a.key_hist = nullptr;
-  m.a.hist_zero = nullptr;
-  m.a.rank_counts = nullptr;
-  m.a.hist_bins = hist ? mg.hist_bins : 0u;
-  m.a.hist_zero_words = hist ? mg.hist_zero_words : 0u;
-  for (int j = 0; j < 3; ++j) m.hist[j] = hist ? mg.hist[j] : nullptr;
-  m.hist_rot = mg.hist_rot;
-  m.parts[0] = mg.parts[0];
-  m.parts[1] = mg.parts[1];
-  m.stats[0] = mg.stats[0];
-  m.stats[1] = mg.stats[1];
-  m.gens = mg.gens;
-  m.bar = mg.barrier;
-  PGA_HIP_CHECK(hipMemsetAsync(mg.barrier, 0, 4, s));
-  hipLaunchKernelGGL(kernel, t.grid, t.block, t.lds + (hist ? 4u * mg.hist_bins : 0u), s, m);
-  binary_hist_written() = hist;
-  return t.grid;
-}
-
-template <int GS, int OBJ>
-uint32_t launch_multi(const GenArgs& a, const MultiGenArgs& mg, hipStream_t s) {
-  if constexpr (OBJ == OBJ_ONEMAX || OBJ == OBJ_LEADING_ONES || OBJ == OBJ_TRAP) {
-    uint32_t gs = 0;
-    bool full = false, dense = false;
-    if (a.chunks > (uint32_t)GS || !binary_tp_plan(a, gs, full, dense) || gs != (uint32_t)GS) return 0;
-    if (a.key_cur == nullptr || a.key_next == nullptr || a.n_elite > 1 ||
-        !(a.selection == SEL_TOURNAMENT || a.selection == SEL_RANDOM))
-      return 0;
-    if (full) {
-      if (dense) return go_tp_multi(binary_gen_tp_multi<GS, OBJ, true, true>, a, mg, s);
-      return go_tp_multi(binary_gen_tp_multi<GS, OBJ, true, false>, a, mg, s);
-    }
-    if (dense) return go_tp_multi(binary_gen_tp_multi<GS, OBJ, false, true>, a, mg, s);
-    return go_tp_multi(binary_gen_tp_multi<GS, OBJ, false, false>, a, mg, s);
-  }
-  (void)a;
-  (void)mg;
-  (void)s;
-  return 0;
 }
 
 template <int GS, int OBJ>
@@ -178,16 +122,6 @@ uint32_t binary_launch_group<PGA_BIN_GS>(int mode, const GenArgs& a, unsigned lo
   return launch_obj<PGA_BIN_GS>(mode, a, best_parts, s);
 }
 
-template <>
-uint32_t binary_launch_multi_group<PGA_BIN_GS>(const GenArgs& a, const MultiGenArgs& mg, hipStream_t s) {
-  switch (a.objective) {
-    case OBJ_ONEMAX: return launch_multi<PGA_BIN_GS, OBJ_ONEMAX>(a, mg, s);
-    case OBJ_TRAP: return launch_multi<PGA_BIN_GS, OBJ_TRAP>(a, mg, s);
-    case OBJ_LEADING_ONES: return launch_multi<PGA_BIN_GS, OBJ_LEADING_ONES>(a, mg, s);
-    default: return 0;
-  }
-}
-
 #if defined(PGA_TP_TIMING) && PGA_BIN_GS == 8
 // (only the headline group size's translation unit defines the dump)
 // experiment builds: mean per-wave cycles of the tournament / breed phases of
@@ -209,20 +143,6 @@ extern "C" void pga_tp_timing_dump(uint32_t nwaves) {
     rt_max = std::max(rt_max, h[i][5]);
     st_max = std::max(st_max, h[i][4]);
     nw = i + 1;
-  }
-  {  // producers (waves that ran tournaments) vs breed-only waves
-    double c[2][5] = {{0}};
-    for (uint32_t i = 0; i < nwaves && i < kMaxGrid * 4; ++i) {
-      if (h[i][2] == 0) continue;
-      const int k = h[i][0] > 0 ? 0 : 1;
-      c[k][0] += 1; c[k][1] += (double)h[i][0]; c[k][2] += (double)h[i][1]; c[k][3] += (double)h[i][7];
-      c[k][4] += (double)h[i][3];
-    }
-    for (int k = 0; k < 2; ++k)
-      if (c[k][0] > 0)
-        std::printf("{\"tp_%s\": {\"waves\": %.0f, \"tourn_cycles\": %.0f, \"breed_cycles\": %.0f, \"spin_cycles\": %.0f, "
-                    "\"children\": %.0f}}\n", k ? "breeders" : "producers", c[k][0], c[k][1] / c[k][0],
-                    c[k][2] / c[k][0], c[k][3] / c[k][0], c[k][4] / c[k][0]);
   }
   std::printf("{\"tp_timing\": {\"waves\": %.0f, \"tourn_cycles\": %.0f, \"breed_cycles\": %.0f, "
               "\"wave_cycles\": %.0f, \"max_wave_cycles\": %.0f, \"tourn_frac\": %.3f, "

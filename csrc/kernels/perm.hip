@@ -31,20 +31,6 @@ namespace {
 
 using namespace dev;
 constexpr uint16_t kNone = 0xFFFF;
-// experiment builds only (tools/variants.sh): tournaments, crossover or the
-// tour evaluation switched off in perm_gen_fast, to split its time
-#ifndef PGA_PERM_NOSEL
-#define PGA_PERM_NOSEL 0
-#endif
-#ifndef PGA_PERM_NOXO
-#define PGA_PERM_NOXO 0
-#endif
-#ifndef PGA_PERM_PF  // parent rows one step ahead
-#define PGA_PERM_PF 1
-#endif
-#ifndef PGA_PERM_NOEVAL
-#define PGA_PERM_NOEVAL 0
-#endif
 constexpr uint32_t kHdrF = 144;  // floats: red u64[4] (8 floats) | elite | pad  (16-aligned)
 
 inline uint32_t perm_max_length(bool euc) {  // longest genome the one-individual-per-block kernel holds in LDS
@@ -514,16 +500,12 @@ __device__ __forceinline__ void perm_gen_fast_body(GenArgs a, unsigned long long
       const u32x4 b0 = draw(a.key, ST_CHILD, cj, 0);
       const LanePool<GS> lpool{draw(a.key, ST_CHILD, cj, 1), draw(a.key, ST_CHILD, cj, 2)};
       select_parents<GS, LanePool<GS>>(a, lpool, cj, PA, PB);
-#if PGA_PERM_NOSEL  // experiment builds: parents without tournaments
-      PA = cj;
-      PB = (cj ^ 1u) < S32 ? (cj ^ 1u) : cj;
-#endif
       const bool elite = cj < a.n_elite;
       if (elite) {
         PA = a.elite_idx ? a.elite_idx[cj] : *lds_elite;
         PB = PA;
       }
-      const bool xo = !PGA_PERM_NOXO && !elite && xo_kind && do_crossover(a, b0.x);  // W_XOPROB
+      const bool xo = !elite && xo_kind && do_crossover(a, b0.x);  // W_XOPROB
       uint32_t lo, hi;
       perm_segment(b0.y, b0.z, L, lo, hi);  // W_CUT1, W_CUT2
       const bool mut = !elite && mut_on && lpool.b1.x < a.mut_ind_thresh;  // W_MUTIND
@@ -533,8 +515,8 @@ __device__ __forceinline__ void perm_gen_fast_body(GenArgs a, unsigned long long
       PX = mi | (mj << 16);
     }
     const uint32_t nst = ((S32 - bb < U ? S32 - bb : U) + NG - 1) / NG;
-    uint4 nA, nB;  // the next step's parent chunks
-    if (PGA_PERM_PF) {
+    uint4 nA, nB;  // the next step's parent chunks (loaded one step ahead)
+    {
       const uint32_t pa = (uint32_t)__shfl((int)PA, (int)g, 64), pb = (uint32_t)__shfl((int)PB, (int)g, 64);
       nA = cur[(uint64_t)pa * rs + qc];
       nB = cur[(uint64_t)pb * rs + qc];
@@ -545,13 +527,8 @@ __device__ __forceinline__ void perm_gen_fast_body(GenArgs a, unsigned long long
       const bool valid = child < S32;  // group-uniform
       const uint32_t jl = NG * t + g;   // the child's SELECT lane
       const uint32_t pa = (uint32_t)__shfl((int)PA, (int)jl, 64);
-      if (!PGA_PERM_PF) {
-        const uint32_t pb = (uint32_t)__shfl((int)PB, (int)jl, 64);
-        nA = cur[(uint64_t)pa * rs + qc];
-        nB = cur[(uint64_t)pb * rs + qc];
-      }
       const uint4 Av = nA, Bv = nB;
-      if (PGA_PERM_PF && t + 1 < nst) {  // wave-uniform: issue step t + 1's rows now
+      if (t + 1 < nst) {  // wave-uniform: issue step t + 1's rows now
         const uint32_t j = jl + NG;
         const uint32_t na = (uint32_t)__shfl((int)PA, (int)j, 64), nb = (uint32_t)__shfl((int)PB, (int)j, 64);
         nA = cur[(uint64_t)na * rs + qc];
@@ -670,7 +647,7 @@ __device__ __forceinline__ void perm_gen_fast_body(GenArgs a, unsigned long long
       wave_sync();  // the next child of this group rewrites C / T
 
       if (valid && have) nxt[(uint64_t)child * rs + q] = Cv;
-      if (!elite && !PGA_PERM_NOEVAL) {
+      if (!elite) {
         // edge of gene e: to gene e + 1, the next lane's first city (e = 7),
         // or the tour's first city (position L - 1); every lookup of the 8
         // issued before the sum, which keeps perm_kernel's order (e = 0..7

@@ -105,17 +105,6 @@ uint32_t tp_skew_units(const TpGeom& t, uint64_t S) {
   return d * 4 < units ? d : 0u;
 }
 
-uint32_t tp_pool_units(const TpGeom& t, uint64_t S) {
-  // PGA_TP_POOL = d: 1/d of each block's units in the pair pool (default 0: none)
-  static const uint32_t d = [] {
-    const char* e = std::getenv("PGA_TP_POOL");
-    return e ? (uint32_t)std::strtoul(e, nullptr, 10) : 0u;  // off by default (tp.hpp)
-  }();
-  if (d == 0 || t.block != dev::kTpMaxWaves * 64 || t.grid < 2) return 0;
-  const uint64_t per = (S + t.grid - 1) / t.grid, units = (per + t.unit - 1) / t.unit;
-  return (uint32_t)(units / d);
-}
-
 TpGeom tp_geometry_occ(uint64_t S, uint32_t islands, uint32_t occ4, uint32_t ng, uint32_t pseg) {
   if (islands == 0) islands = 1;
   if (ng == 0 || ng > 64) ng = 64;
@@ -409,10 +398,9 @@ __global__ __launch_bounds__(kBlock) void prefix_final_int_kernel(const float* s
 // Spans of 32 buckets or more (one individual holding >= 32/S of the total
 // weight) are queued in LDS and filled by the whole block, so no thread loops
 // over a heavy individual's buckets.
-// cov: kGuideCovered, or 0 (no covered flags: S >= 2^31, or PGA_ROUL_COVER=0)
-// gsh 1: the packed table (GenArgs::roul_packed): guide[b] at word 2 b, cumfit[i] at word 2 i + 1
+// cov: kGuideCovered, or 0 (no covered flags: S >= 2^31)
 __global__ __launch_bounds__(kBlock) void roulette_guide_kernel(const float* c, uint64_t S, const float* meta,
-                                                                 uint32_t* guide, uint32_t cov, uint32_t gsh) {
+                                                                 uint32_t* guide, uint32_t cov) {
   __shared__ uint4 spans[kBlock];
   __shared__ uint32_t nsp;
   const float scale = meta[0];
@@ -423,12 +411,11 @@ __global__ __launch_bounds__(kBlock) void roulette_guide_kernel(const float* c, 
     const uint64_t i = t0 + threadIdx.x;
     if (i < S) {
       const float ci = c[i];
-      if (gsh) guide[2 * i + 1] = __builtin_bit_cast(uint32_t, ci);
       const uint32_t hi = roulette_bucket(ci, scale, B);
       const uint32_t lo = i ? roulette_bucket(c[i - 1], scale, B) + 1u : 0u;
       if (hi >= lo) {
         if (hi - lo < 32u) {
-          for (uint32_t b = lo; b <= hi; ++b) guide[b << gsh] = (uint32_t)i | (b < hi ? cov : 0u);
+          for (uint32_t b = lo; b <= hi; ++b) guide[b] = (uint32_t)i | (b < hi ? cov : 0u);
         } else {
           spans[atomicAdd(&nsp, 1u)] = make_uint4(lo, hi, (uint32_t)i, 0u);
         }
@@ -438,7 +425,7 @@ __global__ __launch_bounds__(kBlock) void roulette_guide_kernel(const float* c, 
     const uint32_t n = nsp;
     for (uint32_t k = 0; k < n; ++k) {
       const uint4 sp = spans[k];
-      for (uint32_t b = sp.x + threadIdx.x; b <= sp.y; b += kBlock) guide[b << gsh] = sp.z | (b < sp.y ? cov : 0u);
+      for (uint32_t b = sp.x + threadIdx.x; b <= sp.y; b += kBlock) guide[b] = sp.z | (b < sp.y ? cov : 0u);
     }
     __syncthreads();
   }
@@ -462,7 +449,7 @@ __global__ __launch_bounds__(kRoulThreads) void roulette_fused_kernel(const floa
                                                                       const float* __restrict__ parts, uint32_t unit,
                                                                       uint32_t skew, float* __restrict__ cumfit,
                                                                       uint32_t* __restrict__ guide, float* meta,
-                                                                      uint32_t cov, uint32_t gsh) {
+                                                                      uint32_t cov) {
   __shared__ unsigned long long red[kRoulThreads / 64];
   __shared__ float fred[kRoulThreads / 64];
   __shared__ uint32_t wsum[kRoulThreads / 64];
@@ -560,14 +547,13 @@ __global__ __launch_bounds__(kRoulThreads) void roulette_fused_kernel(const floa
         const float ci = __builtin_bit_cast(float, xch[e]);
         const float prev = e ? __builtin_bit_cast(float, xch[e - 1]) : prev0;
         cumfit[i] = ci;
-        if (gsh) guide[2 * i + 1] = __builtin_bit_cast(uint32_t, ci);
         const uint32_t hi = roulette_bucket(ci, scale, Su);
         const uint32_t lo = i ? roulette_bucket(prev, scale, Su) + 1u : 0u;
         if (hi >= lo) {
           const uint32_t q = hi - lo < 32u ? kRoulSpans : atomicAdd(&nsp, 1u);
           if (q < kRoulSpans) spans[q] = make_uint4(lo, hi, i, 0u);
           else
-            for (uint32_t b = lo; b <= hi; ++b) guide[b << gsh] = i | (b < hi ? cov : 0u);  // short span (or a full queue)
+            for (uint32_t b = lo; b <= hi; ++b) guide[b] = i | (b < hi ? cov : 0u);  // short span (or a full queue)
         }
       }
     }
@@ -575,7 +561,7 @@ __global__ __launch_bounds__(kRoulThreads) void roulette_fused_kernel(const floa
     const uint32_t n = nsp < kRoulSpans ? nsp : kRoulSpans;
     for (uint32_t q = 0; q < n; ++q) {
       const uint4 sp = spans[q];
-      for (uint32_t b = sp.x + t; b <= sp.y; b += kRoulThreads) guide[b << gsh] = sp.z | (b < sp.y ? cov : 0u);
+      for (uint32_t b = sp.x + t; b <= sp.y; b += kRoulThreads) guide[b] = sp.z | (b < sp.y ? cov : 0u);
     }
     __syncthreads();  // (nsp, wsum and xch are reused by the next chunk)
     carry += ctot;
@@ -926,75 +912,14 @@ constexpr uint64_t kLbAgg = 1ull << 62, kLbMask31 = 0x7FFFFFFFull;
 // unless grev: then G is a value-order histogram read only (the generation
 // kernel's fused histogram, GenArgs::key_hist), bin b at G[R - 1 - b] for the
 // smallest, and nothing re-zeroes it
-// Two-pass selection, first pass (fused value-order histogram): the
-// threshold exactly as topk16_select_kernel derives it, and the block's (gt,
-// eq) counts over the same range -> counts[2 b], counts[2 b + 1]
-__global__ __launch_bounds__(kBlock) void topk16_count2_kernel(const uint16_t* k16, uint64_t S, uint64_t per_block,
-                                                               uint32_t R, bool largest, uint32_t k, const uint32_t* G,
-                                                               uint32_t* counts) {
-  __shared__ uint32_t sh_T;
-  __shared__ uint32_t lds[kBlock / 64];
-  const uint32_t per = (R + kBlock - 1) / kBlock;
-  uint32_t mine = 0;
-  for (uint32_t j = 0; j < per; ++j) {
-    const int64_t b = (int64_t)R - 1 - (int64_t)threadIdx.x * per - j;
-    if (b >= 0) mine += G[!largest ? R - 1 - b : b];
-  }
-  uint32_t tot;
-  const uint32_t before = block_excl_scan_u(mine, lds, tot);
-  if (before < k && before + mine >= k) {
-    uint32_t acc = before;
-    for (uint32_t j = 0; j < per; ++j) {
-      const int64_t b = (int64_t)R - 1 - (int64_t)threadIdx.x * per - j;
-      if (b < 0) break;
-      const uint32_t c = G[!largest ? R - 1 - b : b];
-      if (acc + c >= k) {
-        sh_T = (uint32_t)b;
-        break;
-      }
-      acc += c;
-    }
-  }
-  __syncthreads();
-  const uint32_t T = largest ? sh_T : sh_T + 0x10000u - R;
-  const uint32_t flip = largest ? 0u : 0xFFFFu;
-  const uint64_t pt = ((per_block + kBlock - 1) / kBlock + 15) / 16 * 16;
-  const uint64_t blo = (uint64_t)blockIdx.x * per_block;
-  const uint64_t bhi = blo + per_block < S ? blo + per_block : S;
-  const uint64_t t0 = blo + threadIdx.x * pt;
-  const uint64_t t1 = t0 + pt < bhi ? t0 + pt : bhi;
-  uint32_t gt = 0, eq = 0;
-  for (uint64_t c0 = t0; c0 < t1; c0 += 16) {
-    uint32_t kv[16];
-    const uint32_t m = load_keys16(k16, c0, t1, kv);
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const uint32_t key = min(kv[e], R - 1) ^ flip;
-      gt += ((m >> e) & 1u) && key > T;
-      eq += ((m >> e) & 1u) && key == T;
-    }
-  }
-  auto add = [](uint32_t x, uint32_t y) { return x + y; };
-  gt = block_reduce(gt, lds, add);
-  eq = block_reduce(eq, lds, add);
-  if (threadIdx.x == 0) {
-    counts[2 * blockIdx.x] = gt;
-    counts[2 * blockIdx.x + 1] = eq;
-  }
-}
-
-// counts (two-pass mode, fused histograms only): the per-block (gt, eq)
-// counts of topk16_count2_kernel, complete before this launch — every block
-// reads its predecessors' instead of publishing and polling status words
 __global__ __launch_bounds__(kBlock) void topk16_select_kernel(const uint16_t* k16, uint64_t S, uint64_t per_block,
                                                                uint32_t R, bool largest, uint32_t k, uint32_t* G,
                                                                uint64_t* status, uint32_t* ctr, uint32_t nblocks,
-                                                               uint32_t* idx_out, TopkMove mv, bool fused,
-                                                               const uint32_t* counts = nullptr) {
+                                                               uint32_t* idx_out, TopkMove mv, bool fused) {
   __shared__ uint32_t sel_pos[kTopkMoveSlots], sel_src[kTopkMoveSlots];  // row moves: output position, source
   __shared__ uint32_t sh_T, sh_need, sh_b;
   __shared__ uint32_t lds[kBlock / 64];
-  if (threadIdx.x == 0) sh_b = counts ? blockIdx.x : atomicAdd(&ctr[0], 1u);
+  if (threadIdx.x == 0) sh_b = atomicAdd(&ctr[0], 1u);
   // threshold bin: thread t owns bins [R-1 - (t+1)*per + 1, R-1 - t*per], counted from the top
   const uint32_t per = (R + kBlock - 1) / kBlock;
   uint32_t mine = 0;
@@ -1043,17 +968,12 @@ __global__ __launch_bounds__(kBlock) void topk16_select_kernel(const uint16_t* k
   uint32_t og = block_excl_scan_u(gt, lds, bg);
   __syncthreads();
   uint32_t oe = block_excl_scan_u(eq, lds, be);
-  if (threadIdx.x == 0 && !counts)
+  if (threadIdx.x == 0)
     __hip_atomic_store(&status[b], kLbAgg | ((uint64_t)bg << 31) | (uint64_t)be, __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
   // block prefix = sum of the predecessors' aggregates, read in parallel
   uint32_t pg = 0, pe = 0;
   for (uint32_t j = threadIdx.x; j < b; j += kBlock) {
-    if (counts) {
-      pg += counts[2 * j];
-      pe += counts[2 * j + 1];
-      continue;
-    }
     uint64_t w = 0;
     for (uint32_t spins = 0; spins < (1u << 26); ++spins) {  // bound: never hang the device
       w = __hip_atomic_load(&status[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1067,7 +987,7 @@ __global__ __launch_bounds__(kBlock) void topk16_select_kernel(const uint16_t* k
   pe = block_reduce(pe, lds, add);
   // every other block published its aggregate, hence had read the histogram:
   // the last ticket zeroes it for the next selection
-  if (b == nblocks - 1 && !fused && !counts)
+  if (b == nblocks - 1 && !fused)
     for (uint32_t i = threadIdx.x; i < R; i += kBlock) G[i] = 0;
   uint32_t gpos = pg + og, epos = pe + oe;
   // with a row move, the block's selections are listed in LDS first (slot:
@@ -1724,18 +1644,11 @@ void roulette_prefix_launch(const float* scores, uint64_t S, const float* parts,
   PGA_HIP_CHECK(hipGetLastError());
 }
 
-// the guide's covered flag (tp.hpp reads it only while S < 2^31);
-// PGA_ROUL_COVER=0 leaves it out (A/B knob)
-static uint32_t guide_cover_flag(uint64_t S) {
-  static const bool off = [] {
-    const char* e = std::getenv("PGA_ROUL_COVER");
-    return e && e[0] == '0';
-  }();
-  return !off && S <= kGuideIndexMask ? kGuideCovered : 0u;
-}
+// the guide's covered flag (tp.hpp reads it only while S < 2^31)
+static uint32_t guide_cover_flag(uint64_t S) { return S <= kGuideIndexMask ? kGuideCovered : 0u; }
 
 bool roulette_fused_launch(const float* scores, uint64_t S, const float* parts, const TpPartition& part,
-                           uint32_t max_score, float* cumfit, uint32_t* guide, float* ws, hipStream_t s, bool packed) {
+                           uint32_t max_score, float* cumfit, uint32_t* guide, float* ws, hipStream_t s) {
   if (!parts || part.grid == 0 || part.unit == 0 || S == 0 || S > 0xFFFFFFFFull) return false;
   // the largest share (tp_share: ceil(S / grid) in whole units, plus the skew)
   // times the largest score stays below 2^24, so every f32 partial sum is exact
@@ -1745,15 +1658,15 @@ bool roulette_fused_launch(const float* scores, uint64_t S, const float* parts, 
   // a chunk's u32 weight sum: kRoulThreads * kRoulPer * max_score < 2^32
   if ((uint64_t)kRoulThreads * kRoulPer * max_score >= (1ull << 32)) return false;
   hipLaunchKernelGGL(roulette_fused_kernel, part.grid, kRoulThreads, 0, s, scores, S, parts, part.unit, part.skew, cumfit,
-                     guide, ws + kRoulScale, guide_cover_flag(S), packed ? 1u : 0u);
+                     guide, ws + kRoulScale, guide_cover_flag(S));
   PGA_HIP_CHECK(hipGetLastError());
   return true;
 }
 
-void roulette_guide_launch(const float* cumfit, uint64_t S, uint32_t* guide, float* ws, hipStream_t s, bool packed) {
+void roulette_guide_launch(const float* cumfit, uint64_t S, uint32_t* guide, float* ws, hipStream_t s) {
   const uint32_t grid = launch_grid(S, kBlock);
   hipLaunchKernelGGL(roulette_guide_kernel, grid, kBlock, 0, s, cumfit, S, (const float*)(ws + kRoulScale), guide,
-                     guide_cover_flag(S), packed ? 1u : 0u);
+                     guide_cover_flag(S));
   PGA_HIP_CHECK(hipGetLastError());
 }
 
@@ -1849,16 +1762,9 @@ uint32_t topk_launch(const float* scores, const uint16_t* keys16, uint32_t key_r
         // the generation kernel's histogram of these keys, its status words
         // zeroed by that kernel: the select alone (one pass over the keys)
         uint64_t* fst = (uint64_t*)fused->status;
-        // PGA_TOPK_2PASS=1 (A/B): a count launch, then the select reads the
-        // complete counts instead of publishing and polling status words
-        static const bool two = std::getenv("PGA_TOPK_2PASS") && std::getenv("PGA_TOPK_2PASS")[0] == '1';
-        uint32_t* counts = two ? (uint32_t*)fused->status : nullptr;  // 2 words per block <= kTopkStatusWords
-        if (two)
-          hipLaunchKernelGGL(topk16_count2_kernel, cgrid, kBlock, 0, s, keys16, S, pb16, R, largest, k,
-                             fused->hist, counts);
         hipLaunchKernelGGL(topk16_select_kernel, cgrid, kBlock, 0, s, keys16, S, pb16, R, largest, k,
                            const_cast<uint32_t*>(fused->hist), fst, (uint32_t*)(fst + cgrid), cgrid, idx_out,
-                           mv ? *mv : TopkMove{}, true, (const uint32_t*)counts);
+                           mv ? *mv : TopkMove{}, true);
         PGA_HIP_CHECK(hipGetLastError());
         return mv && mv->mode == TopkMove::SCATTER && mv->best_parts ? cgrid : 0u;
       }

@@ -483,15 +483,14 @@ class IslandModel:
         return done
 
     def _fence(self) -> None:
-        """With the engine transport the emigrants are packed on the transport
-        stream, concurrently with the generation after their departure; the
-        generation after THAT overwrites the population they come from, so
-        the compute stream waits for the packing once the first is enqueued."""
+        """With a side stream the emigrants are packed on it, concurrently
+        with the generation after their departure; the generation after THAT
+        overwrites the population they come from, so the compute stream waits
+        for the packing once the first is enqueued.  (The engine transport
+        packs on the compute stream: nothing to order.)"""
         if self._pending is None or self.ga.generation != self._start_gen + 1:
             return
-        if self._pending == "engine":
-            self._ec.fence(self.ga.island)
-        elif self._side is not None:  # the same for the packing on the side stream
+        if self._pending != "engine" and self._side is not None:
             torch.cuda.current_stream(self._side.device).wait_stream(self._side)
 
     def flush(self) -> None:
