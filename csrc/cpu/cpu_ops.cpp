@@ -1,6 +1,7 @@
 // cpu_ops.cpp — CPU reference backend: BINARY encoding + population utilities.
-// Mirrors csrc/kernels/binary.hip and csrc/kernels/util.hip operation by
-// operation (see the comments there for the semantics).
+// Mirrors csrc/kernels/binary.hip, csrc/kernels/util.hip and
+// csrc/kernels/topk.hip operation by operation (see the comments there for
+// the semantics).
 #include <algorithm>
 #include <cmath>
 #include <cstring>

@@ -105,6 +105,47 @@ __device__ __forceinline__ unsigned long long block_reduce_parts_n(const unsigne
   return block_max_u64_n(v, lds, nw);
 }
 
+// block-wide reduction with `op`, result valid in every thread (lds: kBlock / 64 entries)
+template <typename T, typename Op>
+__device__ __forceinline__ T block_reduce(T v, T* lds, Op op) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
+  __syncthreads();
+  if (lane_id() == 0) lds[threadIdx.x >> 6] = v;
+  __syncthreads();
+  T r = lds[0];
+#pragma unroll
+  for (int i = 1; i < kBlock / 64; ++i) r = op(r, lds[i]);
+  return r;
+}
+
+// block-wide exclusive prefix sum; total = the block's sum (lds: kBlock / 64 entries)
+__device__ __forceinline__ uint32_t block_excl_scan_u(uint32_t v, uint32_t* lds, uint32_t& total) {
+  const uint32_t lane = lane_id();
+  uint32_t inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    uint32_t t = (uint32_t)__shfl_up((int)inc, o, 64);
+    if (lane >= (uint32_t)o) inc += t;
+  }
+  __syncthreads();
+  if (lane == 63) lds[threadIdx.x >> 6] = inc;
+  __syncthreads();
+  uint32_t off = 0;
+  total = 0;
+  for (int i = 0; i < kBlock / 64; ++i) {
+    if (i < (int)(threadIdx.x >> 6)) off += lds[i];
+    total += lds[i];
+  }
+  return off + inc - v;
+}
+
+// the u16 tournament key of an integer objective's score: the score clamped
+// to [0, 65535] (NaN -> 0)
+__device__ __forceinline__ uint16_t score_to_key16(float v) {
+  return (uint16_t)(!(v > 0.f) ? 0.f : (v >= 65535.f ? 65535.f : v));
+}
+
 // Fused per-generation statistics: every evaluating kernel keeps a running
 // {min, sum} of the scores its lanes produce and, when GenArgs::stats_parts is
 // set, stores one {min, sum} pair per block next to its packed best (the max),

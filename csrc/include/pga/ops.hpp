@@ -158,7 +158,7 @@ inline uint32_t encoding_launch(int mode, const GenArgs& a, unsigned long long* 
   }
 }
 
-// ---- reductions / selection helpers (util.hip) ----
+// ---- reductions / roulette helpers (util.hip) ----
 // out[0] = max over parts[0..n)
 void reduce_best_launch(const unsigned long long* parts, uint32_t n, unsigned long long* out, hipStream_t s);
 // per-block best over arbitrary scores (for externally evaluated populations)
@@ -217,6 +217,7 @@ void rank_order16_launch(const uint16_t* keys16, uint64_t S, uint32_t key_range,
 // the next rank_order16_launch run with counts_ready, skipping its count pass.
 constexpr uint32_t kRankTile = 4096;
 uint32_t* rank_order16_counts(void* workspace, uint64_t S, uint32_t key_range);
+// ---- selection and migration (topk.hip) ----
 // top-k by score (descending, ties -> lower index); idx_out[k]; workspace: topk_workspace_bytes(S)
 size_t topk_workspace_bytes(uint64_t S, uint32_t k);
 // sorted = false: the k indices in selection order (keys above the threshold by
@@ -260,7 +261,7 @@ uint32_t topk_launch(const float* scores, const uint16_t* keys16, uint32_t key_r
                      bool largest, bool sorted, uint32_t* idx_out, void* workspace, hipStream_t s,
                      const TopkMove* mv = nullptr, const TopkFused* fused = nullptr);
 // rows: out[i] = rows[idx[i]] (row_words 32-bit words per row), optional scores
-// MIG_STRIPE migration (util.hip): stripe i of k = individuals [i*S/k, (i+1)*S/k).
+// MIG_STRIPE migration: stripe i of k = individuals [i*S/k, (i+1)*S/k).
 // emigrate: the best of every stripe (ties: lowest index) -> out rows/scores[i].
 // immigrate: in row/score i replaces the worst of stripe i (ties: lowest
 // index), the tournament key follows, and the kernel writes the island's new

@@ -301,6 +301,26 @@ def test_gpu_topk_selection_order_many_blocks(S):
             assert torch.equal(got, torch.cat([gt, eq])), (k, largest)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("S,ks", [(4099, (1, 4099 // 3, 4099)), (15, (1, 7, 15))])
+def test_gpu_topk_selection_order_edges(S, ks):
+    """The same order at the edges of the u16 select's ranges: S = 4099
+    crosses one block boundary and ends in a 3-key unaligned chunk, S = 15 is
+    less than one 16-key chunk; k = 1, a part and everything, each selection
+    twice in a row (histogram / ticket reset)."""
+    ga = pga.GeneticAlgorithm(pga.models.OneMax(64), S, seed=11, device=DEV)
+    sc = ga.scores.cpu()
+    for k in ks:
+        for largest in (True, False):
+            key = sc if largest else -sc
+            T = key.sort(descending=True).values[k - 1]
+            gt = (key > T).nonzero().flatten()
+            eq = (key == T).nonzero().flatten()[: k - gt.numel()]
+            for _ in range(2):
+                got = ga.island.topk(k, largest, False).cpu().long()
+                assert torch.equal(got, torch.cat([gt, eq])), (k, largest)
+
+
 @pytest.mark.parametrize("S", [5000, 300000])
 def test_topk_keys_above_range(S):
     """Scores outside the objective's range (a checkpoint's or an unvalidated
@@ -324,11 +344,13 @@ def test_topk_keys_above_range(S):
         assert len(low) == k and len(set(low)) == k and all(0 <= i < S for i in low)
 
 
-@pytest.mark.parametrize("S,k", [(5000, 50), (1 << 20, 10486)])
+@pytest.mark.parametrize("S,k", [(5000, 50), (1 << 20, 10486), (8192, 6000)])
 def test_fused_migration_matches_unfused(S, k):
     """Island.emigrate / immigrate (selection kernel with the row gather /
     scatter fused in) == topk + gather / topk + scatter, bit for bit, and the
-    victims' tournament keys follow their new scores."""
+    victims' tournament keys follow their new scores.  (8192, 6000): two
+    select blocks of ~3000 selections each, more than the LDS slot list
+    holds, so the rest is moved row by row."""
     kw = dict(seed=9, device=DEV, elitism=1)
     a = pga.GeneticAlgorithm(pga.models.OneMax(1024), S, **kw)
     b = pga.GeneticAlgorithm(pga.models.OneMax(1024), S, **kw)
@@ -483,12 +505,13 @@ def test_gpu_topk32_selection_order(S, dist):
             assert torch.equal(got, torch.cat([gt, eq])), (k, largest)
 
 
-@pytest.mark.parametrize("S,k", [(5000, 50), (1 << 20, 10486)])
+@pytest.mark.parametrize("S,k", [(5000, 50), (1 << 20, 10486), (8192, 6000)])
 @pytest.mark.parametrize("prob", ["rastrigin", "tsp"])
 def test_fused_migration_matches_unfused_f32(S, k, prob):
     """f32-score islands (REAL, PERMUTATION): Island.emigrate / immigrate
     (the radix select with the row gather / scatter and the new best partials
-    fused in) == topk + gather / topk + scatter + best pass, bit for bit."""
+    fused in) == topk + gather / topk + scatter + best pass, bit for bit.
+    (8192, 6000): more selections per block than the LDS slot list holds."""
     mk = {"rastrigin": lambda: pga.models.Rastrigin(30),
           "tsp": lambda: pga.models.TSP.random_euclidean(64, seed=2)}[prob]
     S = S if prob == "rastrigin" else min(S, 1 << 18)
