@@ -438,6 +438,27 @@ int pga_set_rank_pressure(pga_t* p, population_t* pop, float sp) {
   });
 }
 
+int pga_set_local_search(pga_t* p, population_t* pop, enum pga_local_search kind, unsigned moves, float prob) {
+  if (!valid_pop(p, pop)) return -1;
+  return guard_r<int>(p, -1, [&]() {
+    pga::Config c = pop->isl->config();
+    c.local_search = (int32_t)kind;
+    c.ls_moves = moves;
+    c.ls_prob = prob;
+    pop->isl->set_operators(c);
+    return 0;
+  });
+}
+
+int pga_local_search(pga_t* p, population_t* pop) {
+  if (!valid_pop(p, pop)) return -1;
+  return guard_r<int>(p, -1, [&]() {
+    pop->isl->stream = p->stream;
+    pop->isl->local_search(pop->isl->config().ls_moves, pop->isl->config().ls_prob);
+    return 0;
+  });
+}
+
 // -------------------------------------------------------------------- stages
 void pga_evaluate(pga_t* p, population_t* pop) {
   if (!valid_pop(p, pop)) return;

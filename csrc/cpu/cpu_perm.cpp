@@ -144,5 +144,60 @@ uint32_t perm_run(int mode, const GenArgs& a, unsigned long long* best_parts) {
   return 1;
 }
 
+// 2-opt local search stage (perm_ops.hpp two_opt_*), mirror of perm_ls.hip:
+// the same pairs, gains and tie-break, the same edge-length bookkeeping and
+// the score of MODE_EVAL above for every row that moved
+void perm_local_search(const LsArgs& a) {
+  const uint32_t L = a.L, nch = a.chunks, GS = group_size(nch);
+  const uint64_t rh = 2ull * a.row_words;  // u16 per row
+  const bool open = a.objective == OBJ_TSP_OPEN, euc = a.objective == OBJ_TSP_EUC;
+  uint16_t* rows = (uint16_t*)a.rows;
+  const auto dist = [&](uint32_t u, uint32_t w) -> float {
+    u = std::min(u, L - 1);
+    w = std::min(w, L - 1);
+    return euc ? tsp_euc_dist(a.obj_data, u, w) : a.obj_data[(size_t)u * L + w];
+  };
+  parallel_for(a.S, 16, [&](uint64_t n_begin, uint64_t n_end, unsigned) {
+    std::vector<float> el(L);
+    for (uint64_t n = n_begin; n < n_end; ++n) {
+      if (!ls_selected(a, n)) continue;
+      uint16_t* t = rows + n * rh;
+      for (uint32_t p = 0; p < L; ++p) el[p] = (open && p == L - 1) ? 0.f : dist(t[p], t[(p + 1) % L]);
+      bool moved = false;
+      for (uint32_t m = 0; m < a.moves; ++m) {
+        float bg = 0.f;  // the first maximum in (i, j) order; a NaN gain never passes the strict >
+        uint32_t bp = 0;
+        for (uint32_t i = 0; i + 2 < L; ++i) {
+          const uint32_t jmax = two_opt_jmax(i, L, open);
+          for (uint32_t j = i + 2; j <= jmax; ++j) {
+            const bool closing = open && j == L - 1;
+            const float dac = dist(t[i], t[j]), dbe = closing ? 0.f : dist(t[i + 1], t[(j + 1) % L]);
+            const float g = two_opt_gain(el[i], el[j], dac, dbe);
+            if (g > bg) {
+              bg = g;
+              bp = i * L + j;
+            }
+          }
+        }
+        const unsigned long long best = two_opt_key(bg, bp);
+        if (best == 0) break;
+        const uint32_t pr = two_opt_pair(best), i = pr / L, j = pr % L;
+        const float nac = dist(t[i], t[j]);
+        const float nbe = (open && j == L - 1) ? 0.f : dist(t[i + 1], t[(j + 1) % L]);
+        std::reverse(t + i + 1, t + j + 1);
+        std::reverse(el.begin() + i + 1, el.begin() + j);
+        el[i] = nac;
+        el[j] = nbe;
+        moved = true;
+      }
+      if (!moved) continue;
+      float lane[64] = {0};
+      const uint32_t last = open ? L - 1 : L;
+      for (uint32_t p = 0; p < last; ++p) lane[(p / 8) % GS] += el[p];
+      a.scores[n] = -butterfly_sum(lane, GS);
+    }
+  });
+}
+
 }  // namespace cpu
 }  // namespace pga

@@ -9,6 +9,7 @@
 
 #include "pga/cpu.hpp"
 #include "pga/ops.hpp"
+#include "pga/perm_ops.hpp"
 #include "pga/trace.hpp"
 
 namespace pga {
@@ -162,6 +163,12 @@ void Island::set_operators(const Config& c) {
   if (c.selection < SEL_TOURNAMENT || c.selection > SEL_RANK) throw std::invalid_argument("unknown selection");
   if (c.selection == SEL_RANK && !(c.rank_pressure >= 1.f && c.rank_pressure <= 2.f))
     throw std::invalid_argument("rank pressure must be in [1, 2]");
+  if (c.local_search != LS_NONE && c.local_search != LS_TWO_OPT) throw std::invalid_argument("unknown local search");
+  if (c.local_search == LS_TWO_OPT) {
+    if (c.encoding != ENC_PERMUTATION) throw std::invalid_argument("2-opt local search needs the PERMUTATION encoding");
+    if (c.objective != OBJ_TSP && c.objective != OBJ_TSP_OPEN && c.objective != OBJ_TSP_EUC)
+      throw std::invalid_argument("2-opt local search needs a built-in TSP objective");
+  }
   const float old_rate = cfg_.mut_rate;
   const int32_t old_mut = cfg_.mutation;
   cfg_ = c;
@@ -279,6 +286,62 @@ void Island::prepare_objective() {
   }
   qubo_pack_launch((const float*)obj_data_[0].ptr, cfg_.L, (int8_t*)qubo_qt_.ptr, stream);
   qubo_version_ = obj_version_;
+}
+
+bool Island::matrix_symmetric() {
+  if (sym_version_ != obj_version_) {
+    sym_version_ = obj_version_;
+    const uint32_t L = cfg_.L;
+    const float* d = obj_host0_.data();
+    bool sym = obj_host0_.size() >= (size_t)L * L;
+    for (uint32_t i = 0; sym && i < L; ++i)
+      for (uint32_t j = 0; sym && j < i; ++j)
+        sym = std::memcmp(&d[(size_t)i * L + j], &d[(size_t)j * L + i], sizeof(float)) == 0;
+    sym_ok_ = sym;
+  }
+  return sym_ok_;
+}
+
+void Island::local_search(uint32_t moves, float prob) {
+  TraceRange tr("pga.local_search");
+  if (cfg_.encoding != ENC_PERMUTATION) throw std::invalid_argument("2-opt local search needs the PERMUTATION encoding");
+  if (jit_) throw std::invalid_argument("2-opt local search needs a built-in TSP objective, not a JIT objective");
+  const bool euc = cfg_.objective == OBJ_TSP_EUC;
+  if (!euc && cfg_.objective != OBJ_TSP && cfg_.objective != OBJ_TSP_OPEN)
+    throw std::invalid_argument("2-opt local search needs a built-in TSP objective");
+  if (obj_len_[0] < (euc ? 2ull * cfg_.L : (size_t)cfg_.L * cfg_.L))
+    throw std::invalid_argument("2-opt local search: the objective data is not set");
+  if (!euc && !matrix_symmetric())
+    throw std::invalid_argument("2-opt local search needs a symmetric distance matrix");
+  if (!(prob == prob)) throw std::invalid_argument("local search probability is NaN");
+  prepare_objective();
+  LsArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.rows = rows_[cur_].ptr;
+  a.scores = (float*)scores_[cur_].ptr;
+  a.S = cfg_.S;
+  a.L = cfg_.L;
+  a.row_words = row_words_;
+  a.chunks = chunks_;
+  a.key.k0 = (uint32_t)cfg_.seed;
+  a.key.k1 = (uint32_t)(cfg_.seed >> 32) ^ (epoch_ * 0x9E3779B9u);
+  a.key.gen = gen_;
+  a.key.island = cfg_.island;
+  a.objective = cfg_.objective;
+  a.obj_data = (const float*)obj_data_[0].ptr;
+  if (!euc && aux_kind_ && aux_on_) {
+    a.obj_aux = obj_aux_.ptr;
+    a.obj_aux_kind = aux_kind_;
+    a.obj_aux_bytes = aux_bytes_;
+  }
+  a.moves = moves;
+  a.always = prob >= 1.f ? 1u : 0u;
+  a.thresh = prob_thresh(prob);
+  if (on_gpu()) perm_ls_launch(a, stream);
+  else cpu::perm_local_search(a);
+  // rows and scores changed in place: the partials, the fused statistics and
+  // every key derived from the scores follow, as after evaluate()
+  rebest();
 }
 
 GenArgs Island::make_args(int mode) {
@@ -490,6 +553,11 @@ void Island::prepare_generation() {
 
 void Island::run(uint32_t n) {
   TraceRange tr("pga.run");
+  if (cfg_.local_search != LS_NONE) {  // a stage follows every generation: plain launches only
+    if (jit_) throw std::invalid_argument("2-opt local search needs a built-in TSP objective, not a JIT objective");
+    run_plain(n);
+    return;
+  }
   if (run_tiny(n)) return;
   if (on_gpu() && graph_g_ > 0 && !graph_broken_ && !hist_on_ && n >= graph_g_ + 2) {
     const bool fresh = gexec_ && g_cur_ == cur_ && g_epoch_ == epoch_ && g_version_ == version_ &&
@@ -578,6 +646,7 @@ void Island::run_plain(uint32_t n) {
       set_stats_ok(cur_ ^ 1, false);
     }
     swap();
+    if (cfg_.local_search == LS_TWO_OPT) local_search(cfg_.ls_moves, cfg_.ls_prob);
     if (hist_on_ && !hist_manual_ && !capturing_) append_history();
   }
 }
@@ -592,7 +661,7 @@ bool Island::run_batched(const std::vector<Island*>& isls, uint32_t n, hipStream
     return false;
   for (const Island* i : isls) {
     if (!i || !i->on_gpu() || i->device_ != i0->device_ || i->cfg_.encoding != i0->cfg_.encoding || i->jit_ ||
-        i->user_fn_ || i->user_xo_fn_ || i->user_mut_fn_ || i->hist_on_ || i->cfg_.S != i0->cfg_.S || i->cfg_.L != i0->cfg_.L)
+        i->user_fn_ || i->user_xo_fn_ || i->user_mut_fn_ || i->hist_on_ || i->cfg_.local_search != LS_NONE || i->cfg_.S != i0->cfg_.S || i->cfg_.L != i0->cfg_.L)
       return false;
     for (const Island* j : isls)
       if (j != i && j->rows_[0].ptr == i->rows_[0].ptr) return false;  // the same island twice

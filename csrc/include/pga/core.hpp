@@ -90,6 +90,12 @@ enum Objective : int32_t {
 };
 
 // Island migration policy (Island::emigrate / immigrate)
+// Local search stage after each generation (Island::local_search, Config::local_search)
+enum LocalSearch : int32_t {
+  LS_NONE = 0,
+  LS_TWO_OPT = 1,  // PERMUTATION, TSP objectives: best-improvement 2-opt moves (perm_ops.hpp)
+};
+
 enum MigrationPolicy : int32_t {
   MIG_TOPK = 0,    // exact: the top-k emigrate, the bottom-k are replaced (two radix selections)
   MIG_STRIPE = 1,  // the population is cut into k contiguous stripes; stripe i's best
@@ -107,6 +113,7 @@ enum Stream : uint32_t {
   ST_PERM = 7,     // permutation crossover helpers
   ST_SEL = 8,      // BINARY: selection words, 4 per block
   ST_BMUT = 9,     // BINARY: mutation words (positions, per-chunk geometric draws)
+  ST_LS = 10,      // local search: block 0, register .x = the individual's selection test
 };
 
 // Per-child randomness (stream ST_CHILD, one Philox block b per index):
@@ -508,6 +515,23 @@ PGA_HD uint32_t range_mask32(uint32_t base, uint32_t lo, uint32_t hi) {
   uint32_t ml = l >= 32u ? 0xFFFFFFFFu : ((1u << l) - 1u);
   return mh & ~ml;
 }
+
+// Arguments of the local search stage (perm_ls.hip, cpu_perm.cpp
+// perm_local_search): its own small POD, so GenArgs -- the kernarg of every
+// generation kernel and of the JIT bitcode -- keeps its layout.
+struct LsArgs {
+  void* rows;     // current population, improved in place
+  float* scores;  // its scores; rewritten for the rows that moved
+  uint64_t S;
+  uint32_t L, row_words, chunks;
+  RngKey key;     // key.gen: the island's current generation counter
+  int32_t objective;         // OBJ_TSP / OBJ_TSP_OPEN / OBJ_TSP_EUC
+  const float* obj_data;     // L*L distance matrix, or L (x, y) coordinates
+  const void* obj_aux;       // GenArgs::obj_aux (kinds 1 and 3), nullptr: the f32 matrix
+  uint32_t obj_aux_kind, obj_aux_bytes;
+  uint32_t moves;            // at most this many moves per selected individual
+  uint32_t thresh, always;   // selected iff always or the ST_LS word < thresh
+};
 
 // Lanes cooperating on one individual: the smallest power of two >= chunks,
 // capped at one wave.  Part of the SEMANTICS (it fixes the float summation

@@ -48,6 +48,12 @@ struct Config {
   uint32_t n_elite = 0;
   uint64_t seed = 0;
   uint32_t island = 0;
+  // local search stage after every generation of run() / run_until()
+  // (Island::local_search): LS_NONE or LS_TWO_OPT, moves per selected
+  // individual, share of the population selected
+  int32_t local_search = LS_NONE;
+  uint32_t ls_moves = 1;
+  float ls_prob = 1.f;
 };
 
 // words per row and gene chunks for an encoding
@@ -113,6 +119,15 @@ class Island {
   void mutate_stage();        // mutate next in place
   void swap();                // cur <-> next, generation++
   void rebest();              // recompute best partials (and tournament keys) of cur from its scores
+  // 2-opt local search on the current population, in place (perm_ops.hpp
+  // two_opt_*): up to `moves` best-improvement moves on every individual n
+  // with prob >= 1 or draw(key, ST_LS, n, 0).x < prob * 2^32, key.gen = the
+  // current generation counter -- so two calls in one generation select the
+  // same individuals.  Rows that moved get the score evaluate() would give
+  // them; every other row and score is untouched.  Best partials are current
+  // afterwards; the generation counter does not advance.  PERMUTATION with a
+  // TSP objective (matrix objectives: a symmetric matrix), no JIT objective.
+  void local_search(uint32_t moves, float prob);
 
   // ---- queries (synchronise the stream) ----
   unsigned long long best_packed();
@@ -237,6 +252,10 @@ class Island {
   Buffer qubo_qt_;               // QUBO: int8 Q^T packed from objective data slot 0 (GPU)
   uint32_t obj_version_ = 0, qubo_version_ = ~0u;
   void prepare_objective();      // derived objective data (QUBO packing)
+  // slot 0 as an L x L matrix is bitwise symmetric (checked once per data version, both backends)
+  bool matrix_symmetric();
+  uint32_t sym_version_ = ~0u;
+  bool sym_ok_ = false;
   size_t obj_len_[2] = {0, 0};
   std::vector<float> obj_host0_;  // host copy of objective data slot 0 (derived tables)
   Buffer knap_tab_;               // BINARY knapsack: matrix-core digit table (GPU, integer instances)

@@ -125,6 +125,9 @@ uint32_t real_launch(int mode, const GenArgs& a, unsigned long long* best_parts,
 bool real_launch_multi(const GenArgs& a, unsigned long long* const parts[2], float* const stats[2], uint32_t n,
                        hipStream_t s);
 uint32_t perm_launch(int mode, const GenArgs& a, unsigned long long* best_parts, hipStream_t s);
+// 2-opt local search stage (perm_ls.hip): one wave per tour, in place; genomes
+// of at most kPermMaxL cities (longer: std::invalid_argument "too long")
+void perm_ls_launch(const LsArgs& a, hipStream_t s);
 
 // reference-ABI path: thread-per-individual kernel calling user device
 // function pointers (crossover_f / mutate_f / obj_f), REAL encoding only

@@ -36,4 +36,33 @@ PGA_HD void perm_mut_positions(uint32_t w1, uint32_t w2, uint32_t L, uint32_t& i
   if (i > j) { uint32_t t = i; i = j; j = t; }
 }
 
+// ------------------------------------------------ 2-opt local search ---
+// One move on the tour t[0..L): over every pair (i, j), 0 <= i, i + 2 <= j < L
+// (closed tours: not (0, L - 1)), with a = t[i], b = t[i+1], c = t[j],
+// e = t[(j+1) % L],
+//   gain = (d(a,b) + d(c,e)) - (d(a,c) + d(b,e))      in f32, this association
+// d = the value the evaluation sums (the matrix entry, or tsp_euc_dist).  An
+// open path is a closed tour whose closing edge has length 0: for j = L - 1,
+// d(c,e) = d(b,e) = 0.  The pair with the largest gain wins, ties to the
+// smallest i, then the smallest j: the maximum of two_opt_key.  A gain > 0
+// reverses t[i+1 .. j]; otherwise (NaN included) the tour is 2-optimal.
+// fl(x) > fl(y) implies x > y, so every move shortens the true tour and the
+// search ends without an epsilon.  d must be symmetric bit for bit (the
+// reversed edges keep their lengths).
+PGA_HD float two_opt_gain(float dab, float dce, float dac, float dbe) { return (dab + dce) - (dac + dbe); }
+// a candidate's key (0: no candidate); pairs are numbered i * L + j < 2^32
+PGA_HD unsigned long long two_opt_key(float gain, uint32_t pair) {
+  return gain > 0.f ? (((unsigned long long)score_key(gain) << 32) | (0xFFFFFFFFu - pair)) : 0ull;
+}
+PGA_HD uint32_t two_opt_pair(unsigned long long key) { return 0xFFFFFFFFu - (uint32_t)key; }
+// last j paired with i (the closed tour's pair (0, L - 1) shares the city t[0])
+PGA_HD uint32_t two_opt_jmax(uint32_t i, uint32_t L, bool open) { return (i == 0 && !open) ? L - 2 : L - 1; }
+// the Euclidean edge as every evaluation computes it
+PGA_HD float tsp_euc_dist(const float* xy, uint32_t u, uint32_t w) {
+  const float dx = xy[2 * u] - xy[2 * w], dy = xy[2 * u + 1] - xy[2 * w + 1];
+  return __builtin_sqrtf(__builtin_fmaf(dx, dx, dy * dy));
+}
+// individual n takes part in the stage
+PGA_HD bool ls_selected(const LsArgs& a, uint64_t n) { return a.always || draw(a.key, ST_LS, n, 0).x < a.thresh; }
+
 }  // namespace pga

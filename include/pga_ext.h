@@ -63,6 +63,17 @@ int pga_set_bounds(pga_t *p, population_t *pop, float lo, float hi);
 int pga_set_blend_alpha(pga_t *p, population_t *pop, float alpha);
 /* PGA_SEL_RANK: linear ranking pressure sp in [1, 2] (expected copies of the best; default 1.5) */
 int pga_set_rank_pressure(pga_t *p, population_t *pop, float sp);
+/* Local search stage (PERMUTATION with a TSP objective; the matrix objectives
+ * need a symmetric matrix): every generation of pga_run* is followed by up to
+ * `moves` best-improvement 2-opt moves on each individual selected with
+ * probability `prob` (>= 1: everyone; elites included, no tour gets longer).
+ * pga_local_search runs the stage once on the current population with the
+ * values set here (moves 1, prob 1 by default), also with kind NONE; the
+ * generation counter does not advance, and a second call in the same
+ * generation selects the same individuals. */
+enum pga_local_search { PGA_LS_NONE = 0, PGA_LS_TWO_OPT = 1 };
+int pga_set_local_search(pga_t *p, population_t *pop, enum pga_local_search kind, unsigned moves, float prob);
+int pga_local_search(pga_t *p, population_t *pop);
 
 /* ---- queries ---- */
 unsigned long pga_population_size(const population_t *pop);

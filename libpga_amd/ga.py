@@ -33,6 +33,8 @@ MUTATIONS = {
     "swap": C.MUT_SWAP, "inversion": C.MUT_INVERSION, "none": C.MUT_NONE,
 }
 
+LOCAL_SEARCHES = {None: C.LS_NONE, "none": C.LS_NONE, "two_opt": C.LS_TWO_OPT}
+
 
 def default_device() -> torch.device:
     if torch.cuda.is_available():
@@ -89,6 +91,8 @@ class GeneticAlgorithm:
             self._island.set_objective_data(d2, 1)
         # the objective the Python layer evaluates (None: native, fused or JIT)
         self.torch_objective = problem.torch_objective
+        if ops.local_search not in (None, "none") and self.torch_objective is not None:
+            raise ValueError("local search needs a native TSP objective, not a torch objective")
         if getattr(problem, "jit_source", None) is not None:
             if self.device.type == "cuda":
                 self._island.set_jit_objective(problem.kernel())
@@ -112,6 +116,11 @@ class GeneticAlgorithm:
         cfg.sigma = float(ops.sigma)
         cfg.rank_pressure = float(ops.rank_pressure)
         cfg.n_elite = int(ops.elitism)
+        if ops.local_search not in LOCAL_SEARCHES:
+            raise ValueError(f"unknown local search {ops.local_search!r} (None or 'two_opt')")
+        cfg.local_search = LOCAL_SEARCHES[ops.local_search]
+        cfg.ls_moves = int(ops.ls_moves)
+        cfg.ls_prob = float(ops.ls_prob)
 
     def set_operators(self, **kw) -> None:
         for k, v in kw.items():
@@ -153,6 +162,24 @@ class GeneticAlgorithm:
             self._custom_eval()
         else:
             self._island.evaluate()
+
+    def local_search(self, moves: Optional[int] = None, prob: Optional[float] = None) -> None:
+        """One 2-opt local search stage on the current population, in place:
+        up to ``moves`` best-improvement moves on each individual selected
+        with probability ``prob`` (defaults: the operators' ``ls_moves`` /
+        ``ls_prob``).  PERMUTATION with a native TSP objective (a symmetric
+        matrix, or coordinates).  No tour gets longer; rows that moved are
+        rescored, the others are untouched.  The generation counter does not
+        advance, and the selection is a function of (seed, generation,
+        individual): calling the stage twice in one generation selects the
+        same individuals."""
+        if self.torch_objective is not None:
+            raise ValueError("local search needs a native TSP objective, not a torch objective")
+        m = self.operators.ls_moves if moves is None else moves
+        p = self.operators.ls_prob if prob is None else prob
+        if int(m) < 0:
+            raise ValueError("moves must be >= 0")
+        self._island.local_search(int(m), float(p))
 
     def step(self) -> None:
         self.run(1)

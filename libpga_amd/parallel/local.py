@@ -49,6 +49,8 @@ class LocalIslands:
             GeneticAlgorithm(problem, pop_size, seed=seed, island=first_island + i, device=device, **op_overrides)
             for i in range(n_islands)
         ]
+        if self.islands[0].operators.local_search not in (None, "none"):
+            raise ValueError("LocalIslands does not run the local search stage; use IslandModel or a GeneticAlgorithm")
         for ga in self.islands:
             ga.island.migration_policy = migration_policy(policy)
             if policy == "topk" and n_islands > 1:

@@ -16,7 +16,7 @@ COMMON="-O1 -g -fPIC -std=c++17 -Icsrc/include -Iinclude"
 objs=()
 # an object is fresh only if newer than its source AND every header it may include
 HDR=$(ls -t csrc/include/pga/*.hpp include/*.h | sed -n 1p)
-for s in csrc/kernels/binary.hip csrc/kernels/real.hip csrc/kernels/perm.hip csrc/kernels/util.hip csrc/kernels/topk.hip csrc/kernels/compat.hip; do
+for s in csrc/kernels/binary.hip csrc/kernels/real.hip csrc/kernels/perm.hip csrc/kernels/perm_ls.hip csrc/kernels/util.hip csrc/kernels/topk.hip csrc/kernels/compat.hip; do
   o=$O/$(basename $s .hip).o; objs+=($o)
   [ $o -nt $s ] && [ $o -nt $HDR ] || echo "$HIPCC --offload-arch=gfx950 $COMMON -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-omit-frame-pointer -c $s -o $o"
 done > $O/cmds.txt
