@@ -10,6 +10,7 @@
 #include "pga/cpu.hpp"
 #include "pga/ops.hpp"
 #include "pga/perm_ops.hpp"
+#include "pga/qubo_ops.hpp"
 #include "pga/trace.hpp"
 
 namespace pga {
@@ -70,7 +71,7 @@ Island::Island(const Config& cfg, int device) : cfg_(cfg), device_(device) {
 Island::~Island() {
   Buffer* all[] = {&rows_[0],   &rows_[1],     &scores_[0],   &scores_[1],  &best_[0],  &best_[1],   &mut_thr_,
                    &obj_data_[0], &obj_data_[1], &keys_[0], &keys_[1], &elite_idx_, &cumfit_, &cum_ws_, &roul_guide_, &topk_ws_, &stats_,
-                   &out_best_,  &scratch_, &compat_rand_, &ev_parts_, &gen_dev_, &rank_order_, &rank_ws_, &qubo_qt_,
+                   &out_best_,  &scratch_, &compat_rand_, &ev_parts_, &gen_dev_, &rank_order_, &rank_ws_, &qubo_qt_, &qubo_qn_,
                    &knap_tab_, &stats_parts_[0], &stats_parts_[1], &hist_, &qk_ws_, &obj_aux_,
                    &fhist_[0], &fhist_[1], &fhist_[2]};
   drop_graph();
@@ -163,7 +164,10 @@ void Island::set_operators(const Config& c) {
   if (c.selection < SEL_TOURNAMENT || c.selection > SEL_RANK) throw std::invalid_argument("unknown selection");
   if (c.selection == SEL_RANK && !(c.rank_pressure >= 1.f && c.rank_pressure <= 2.f))
     throw std::invalid_argument("rank pressure must be in [1, 2]");
-  if (c.local_search != LS_NONE && c.local_search != LS_TWO_OPT) throw std::invalid_argument("unknown local search");
+  if (c.local_search != LS_NONE && c.local_search != LS_TWO_OPT && c.local_search != LS_ONE_FLIP)
+    throw std::invalid_argument("unknown local search");
+  if (c.local_search == LS_ONE_FLIP && (c.encoding != ENC_BINARY || c.objective != OBJ_QUBO))
+    throw std::invalid_argument("one-flip local search needs the BINARY encoding with the built-in QUBO objective");
   if (c.local_search == LS_TWO_OPT) {
     if (c.encoding != ENC_PERMUTATION) throw std::invalid_argument("2-opt local search needs the PERMUTATION encoding");
     if (c.objective != OBJ_TSP && c.objective != OBJ_TSP_OPEN && c.objective != OBJ_TSP_EUC)
@@ -230,10 +234,11 @@ void Island::prepare_objective() {
   if ((cfg_.objective == OBJ_TSP || cfg_.objective == OBJ_TSP_OPEN) && cfg_.encoding == ENC_PERMUTATION && on_gpu() &&
       aux_version_ != obj_version_) {
     // the matrix for the LDS-resident tour evaluation (perm.hip perm_gen_fast
-    // TBL): an integer matrix (entries in [0, 65535]) as u16 — the strict
-    // lower triangle plus the diagonal when symmetric (kind 1), else the full
-    // matrix (kind 2); any other symmetric matrix as the f32 triangle plus
-    // diagonal (kind 3); an asymmetric float matrix stays in L2 (kind 0)
+    // TBL, which reads it): an integer matrix (entries in [0, 65535]) as u16
+    // -- when symmetric the row-major lower triangle with the diagonal, entry
+    // (i, j <= i) at i (i + 1) / 2 + j (kind 1), else the full matrix (kind
+    // 2); any other symmetric matrix as the f32 lower triangle in the same
+    // layout (kind 3); an asymmetric float matrix stays in L2 (kind 0)
     aux_version_ = obj_version_;
     aux_kind_ = aux_bytes_ = 0;
     const uint32_t L = cfg_.L;
@@ -282,9 +287,11 @@ void Island::prepare_objective() {
   if (lp > kQuboMaxBits) throw std::invalid_argument("QUBO objective supports genomes of at most 1024 bits");
   if (qubo_qt_.bytes < (size_t)lp * lp) {
     release(qubo_qt_);
+    release(qubo_qn_);
     qubo_qt_ = alloc((size_t)lp * lp);
+    qubo_qn_ = alloc((size_t)lp * lp);
   }
-  qubo_pack_launch((const float*)obj_data_[0].ptr, cfg_.L, (int8_t*)qubo_qt_.ptr, stream);
+  qubo_pack_launch((const float*)obj_data_[0].ptr, cfg_.L, (int8_t*)qubo_qt_.ptr, stream, (int8_t*)qubo_qn_.ptr);
   qubo_version_ = obj_version_;
 }
 
@@ -304,7 +311,12 @@ bool Island::matrix_symmetric() {
 
 void Island::local_search(uint32_t moves, float prob) {
   TraceRange tr("pga.local_search");
-  if (cfg_.encoding != ENC_PERMUTATION) throw std::invalid_argument("2-opt local search needs the PERMUTATION encoding");
+  if (cfg_.encoding == ENC_BINARY && cfg_.objective == OBJ_QUBO && cfg_.local_search != LS_TWO_OPT) {
+    one_flip_search(moves, prob);
+    return;
+  }
+  if (cfg_.encoding != ENC_PERMUTATION)
+    throw std::invalid_argument("2-opt local search needs the PERMUTATION encoding (one-flip: BINARY with the QUBO objective)");
   if (jit_) throw std::invalid_argument("2-opt local search needs a built-in TSP objective, not a JIT objective");
   const bool euc = cfg_.objective == OBJ_TSP_EUC;
   if (!euc && cfg_.objective != OBJ_TSP && cfg_.objective != OBJ_TSP_OPEN)
@@ -334,6 +346,7 @@ void Island::local_search(uint32_t moves, float prob) {
     a.obj_aux_kind = aux_kind_;
     a.obj_aux_bytes = aux_bytes_;
   }
+  a.kind = LS_TWO_OPT;
   a.moves = moves;
   a.always = prob >= 1.f ? 1u : 0u;
   a.thresh = prob_thresh(prob);
@@ -342,6 +355,38 @@ void Island::local_search(uint32_t moves, float prob) {
   // rows and scores changed in place: the partials, the fused statistics and
   // every key derived from the scores follow, as after evaluate()
   rebest();
+}
+
+void Island::one_flip_search(uint32_t moves, float prob) {
+  if (jit_) throw std::invalid_argument("one-flip local search needs the built-in QUBO objective, not a JIT objective");
+  if (one_flip_sign(cfg_.obj_f0) == 0)
+    throw std::invalid_argument("one-flip local search: the QUBO score factor (obj_f0) must be non-zero");
+  if (!(prob == prob)) throw std::invalid_argument("local search probability is NaN");
+  prepare_objective();  // (throws when the matrix is not set) both packed matrices on the GPU
+  LsArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.rows = rows_[cur_].ptr;
+  a.scores = (float*)scores_[cur_].ptr;
+  a.S = cfg_.S;
+  a.L = cfg_.L;
+  a.row_words = row_words_;
+  a.chunks = chunks_;
+  a.key.k0 = (uint32_t)cfg_.seed;
+  a.key.k1 = (uint32_t)(cfg_.seed >> 32) ^ (epoch_ * 0x9E3779B9u);
+  a.key.gen = gen_;
+  a.key.island = cfg_.island;
+  a.objective = cfg_.objective;
+  a.obj_data = (const float*)obj_data_[0].ptr;
+  a.qubo_qt = (const int8_t*)qubo_qt_.ptr;
+  a.qubo_qn = (const int8_t*)qubo_qn_.ptr;
+  a.obj_f0 = cfg_.obj_f0;
+  a.kind = LS_ONE_FLIP;
+  a.moves = moves;
+  a.always = prob >= 1.f ? 1u : 0u;
+  a.thresh = prob_thresh(prob);
+  if (on_gpu()) qubo_ls_launch(a, stream);
+  else cpu::qubo_local_search(a);
+  rebest();  // as after the 2-opt stage
 }
 
 GenArgs Island::make_args(int mode) {
@@ -554,7 +599,10 @@ void Island::prepare_generation() {
 void Island::run(uint32_t n) {
   TraceRange tr("pga.run");
   if (cfg_.local_search != LS_NONE) {  // a stage follows every generation: plain launches only
-    if (jit_) throw std::invalid_argument("2-opt local search needs a built-in TSP objective, not a JIT objective");
+    if (jit_)
+      throw std::invalid_argument(cfg_.local_search == LS_ONE_FLIP
+                                      ? "one-flip local search needs the built-in QUBO objective, not a JIT objective"
+                                      : "2-opt local search needs a built-in TSP objective, not a JIT objective");
     run_plain(n);
     return;
   }
@@ -646,7 +694,7 @@ void Island::run_plain(uint32_t n) {
       set_stats_ok(cur_ ^ 1, false);
     }
     swap();
-    if (cfg_.local_search == LS_TWO_OPT) local_search(cfg_.ls_moves, cfg_.ls_prob);
+    if (cfg_.local_search != LS_NONE) local_search(cfg_.ls_moves, cfg_.ls_prob);
     if (hist_on_ && !hist_manual_ && !capturing_) append_history();
   }
 }

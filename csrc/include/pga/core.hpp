@@ -94,6 +94,7 @@ enum Objective : int32_t {
 enum LocalSearch : int32_t {
   LS_NONE = 0,
   LS_TWO_OPT = 1,  // PERMUTATION, TSP objectives: best-improvement 2-opt moves (perm_ops.hpp)
+  LS_ONE_FLIP = 2, // BINARY, OBJ_QUBO: best-improvement single-bit flips (qubo_ops.hpp)
 };
 
 enum MigrationPolicy : int32_t {
@@ -516,22 +517,32 @@ PGA_HD uint32_t range_mask32(uint32_t base, uint32_t lo, uint32_t hi) {
   return mh & ~ml;
 }
 
-// Arguments of the local search stage (perm_ls.hip, cpu_perm.cpp
-// perm_local_search): its own small POD, so GenArgs -- the kernarg of every
-// generation kernel and of the JIT bitcode -- keeps its layout.
+// Arguments of the local search stages (perm_ls.hip / cpu_perm.cpp
+// perm_local_search; qubo_ls.hip / cpu_qubo.cpp qubo_local_search): their own
+// small POD, so GenArgs -- the kernarg of every generation kernel and of the
+// JIT bitcode -- keeps its layout.
 struct LsArgs {
   void* rows;     // current population, improved in place
   float* scores;  // its scores; rewritten for the rows that moved
   uint64_t S;
   uint32_t L, row_words, chunks;
   RngKey key;     // key.gen: the island's current generation counter
-  int32_t objective;         // OBJ_TSP / OBJ_TSP_OPEN / OBJ_TSP_EUC
-  const float* obj_data;     // L*L distance matrix, or L (x, y) coordinates
+  int32_t objective;         // OBJ_TSP / OBJ_TSP_OPEN / OBJ_TSP_EUC, or OBJ_QUBO
+  const float* obj_data;     // L*L distance matrix, L (x, y) coordinates, or the L*L matrix Q
   const void* obj_aux;       // GenArgs::obj_aux (kinds 1 and 3), nullptr: the f32 matrix
   uint32_t obj_aux_kind, obj_aux_bytes;
   uint32_t moves;            // at most this many moves per selected individual
   uint32_t thresh, always;   // selected iff always or the ST_LS word < thresh
+  // LS_ONE_FLIP (GPU): Q^T and Q as int8, padded to qubo_padded_length(L)
+  // square (qt[n * Lp + k] = q[k][n], qn[n * Lp + k] = q[n][k]); the score
+  // factor Config::obj_f0; the stage's kind (LS_TWO_OPT / LS_ONE_FLIP)
+  const int8_t* qubo_qt;
+  const int8_t* qubo_qn;
+  float obj_f0;
+  int32_t kind;
 };
+// individual n takes part in the stage
+PGA_HD bool ls_selected(const LsArgs& a, uint64_t n) { return a.always || draw(a.key, ST_LS, n, 0).x < a.thresh; }
 
 // Lanes cooperating on one individual: the smallest power of two >= chunks,
 // capped at one wave.  Part of the SEMANTICS (it fixes the float summation

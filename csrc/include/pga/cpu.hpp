@@ -30,6 +30,8 @@ uint32_t real_run(int mode, const GenArgs& a, unsigned long long* best_parts);
 uint32_t perm_run(int mode, const GenArgs& a, unsigned long long* best_parts);
 // 2-opt local search stage, bit-identical to perm_ls.hip (any genome length)
 void perm_local_search(const LsArgs& a);
+// one-flip local search stage of OBJ_QUBO (qubo_ops.hpp), bit-identical to qubo_ls.hip
+void qubo_local_search(const LsArgs& a);
 // PMX (op = XO_PMX) or OX1 child of A and B keeping A's segment [lo, hi)
 void perm_crossover(int op, const uint16_t* A, const uint16_t* B, uint32_t L, uint32_t lo, uint32_t hi, uint16_t* C);
 

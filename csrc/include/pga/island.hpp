@@ -49,7 +49,7 @@ struct Config {
   uint64_t seed = 0;
   uint32_t island = 0;
   // local search stage after every generation of run() / run_until()
-  // (Island::local_search): LS_NONE or LS_TWO_OPT, moves per selected
+  // (Island::local_search): LS_NONE, LS_TWO_OPT or LS_ONE_FLIP, moves per selected
   // individual, share of the population selected
   int32_t local_search = LS_NONE;
   uint32_t ls_moves = 1;
@@ -127,6 +127,8 @@ class Island {
   // them; every other row and score is untouched.  Best partials are current
   // afterwards; the generation counter does not advance.  PERMUTATION with a
   // TSP objective (matrix objectives: a symmetric matrix), no JIT objective.
+  // BINARY with OBJ_QUBO runs the one-flip stage instead (qubo_ops.hpp): up to
+  // `moves` best-improvement single-bit flips, the same selection rule.
   void local_search(uint32_t moves, float prob);
 
   // ---- queries (synchronise the stream) ----
@@ -250,10 +252,12 @@ class Island {
   Buffer qk_ws_;
   bool qk_valid_[2] = {false, false};
   Buffer qubo_qt_;               // QUBO: int8 Q^T packed from objective data slot 0 (GPU)
+  Buffer qubo_qn_;               // QUBO: int8 Q in the same padding (one-flip local search, GPU)
   uint32_t obj_version_ = 0, qubo_version_ = ~0u;
   void prepare_objective();      // derived objective data (QUBO packing)
   // slot 0 as an L x L matrix is bitwise symmetric (checked once per data version, both backends)
   bool matrix_symmetric();
+  void one_flip_search(uint32_t moves, float prob);  // local_search() of BINARY / OBJ_QUBO
   uint32_t sym_version_ = ~0u;
   bool sym_ok_ = false;
   size_t obj_len_[2] = {0, 0};

@@ -136,8 +136,12 @@ uint32_t compat_launch(int mode, const GenArgs& a, unsigned long long* best_part
 // QUBO on the int8 matrix cores (qubo.hip): genomes up to kQuboMaxBits bits
 constexpr uint32_t kQuboMaxBits = 1024;
 uint32_t qubo_padded_length(uint32_t L);  // 64, 128, 256, 512 or 1024
-// qt: Lp x Lp int8 (Lp = qubo_padded_length(L)), Q^T of round/clamped q
-void qubo_pack_launch(const float* q, uint32_t L, int8_t* qt, hipStream_t s);
+// qt: Lp x Lp int8 (Lp = qubo_padded_length(L)), Q^T of round/clamped q;
+// qn (optional): Q itself in the same padding (the one-flip stage's second operand)
+void qubo_pack_launch(const float* q, uint32_t L, int8_t* qt, hipStream_t s, int8_t* qn = nullptr);
+// one-flip local search stage (qubo_ls.hip): 16 selected individuals per wave
+// tile, g on the int8 matrix cores, in place; needs a.qubo_qt and a.qubo_qn
+void qubo_ls_launch(const LsArgs& a, hipStream_t s);
 // scores[i] = sign * x_i^T Q x_i for S bit rows; per-block bests -> parts; returns the grid
 uint32_t qubo_eval_launch(const void* rows, uint32_t row_words, uint64_t S, uint32_t L, const int8_t* qt, float sign,
                           float* scores, unsigned long long* parts, hipStream_t s);

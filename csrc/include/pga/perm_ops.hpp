@@ -62,7 +62,5 @@ PGA_HD float tsp_euc_dist(const float* xy, uint32_t u, uint32_t w) {
   const float dx = xy[2 * u] - xy[2 * w], dy = xy[2 * u + 1] - xy[2 * w + 1];
   return __builtin_sqrtf(__builtin_fmaf(dx, dx, dy * dy));
 }
-// individual n takes part in the stage
-PGA_HD bool ls_selected(const LsArgs& a, uint64_t n) { return a.always || draw(a.key, ST_LS, n, 0).x < a.thresh; }
 
 }  // namespace pga

@@ -155,12 +155,15 @@ __global__ __launch_bounds__(kBlock, 2) void qubo_eval_kernel(const uint32_t* __
   if (threadIdx.x == 0) parts[blockIdx.x] = b;
 }
 
-// Q (row-major L x L floats, integers) -> int8 Q^T padded to Lp x Lp
-__global__ __launch_bounds__(kBlock) void qubo_pack_kernel(const float* q, uint32_t L, uint32_t Lp, int8_t* qt) {
+// Q (row-major L x L floats, integers) -> int8 Q^T padded to Lp x Lp, and
+// (qn != nullptr) Q itself in the same padding, for the one-flip stage (qubo_ls.hip)
+__global__ __launch_bounds__(kBlock) void qubo_pack_kernel(const float* q, uint32_t L, uint32_t Lp, int8_t* qt,
+                                                           int8_t* qn) {
   for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < (uint64_t)Lp * Lp;
        i += (uint64_t)gridDim.x * kBlock) {
     const uint32_t n = (uint32_t)(i / Lp), k = (uint32_t)(i % Lp);
     qt[i] = (n < L && k < L) ? (int8_t)qubo_coef(q[(uint64_t)k * L + n]) : (int8_t)0;
+    if (qn) qn[i] = (n < L && k < L) ? (int8_t)qubo_coef(q[(uint64_t)n * L + k]) : (int8_t)0;
   }
 }
 
@@ -196,10 +199,10 @@ uint32_t qubo_padded_length(uint32_t L) {
   return lp;
 }
 
-void qubo_pack_launch(const float* q, uint32_t L, int8_t* qt, hipStream_t s) {
+void qubo_pack_launch(const float* q, uint32_t L, int8_t* qt, hipStream_t s, int8_t* qn) {
   const uint32_t Lp = qubo_padded_length(L);
   if (Lp > kQuboMaxBits) throw std::invalid_argument("QUBO objective supports genomes of at most 1024 bits");
-  hipLaunchKernelGGL(qubo_pack_kernel, 512, kBlock, 0, s, q, L, Lp, qt);
+  hipLaunchKernelGGL(qubo_pack_kernel, 512, kBlock, 0, s, q, L, Lp, qt, qn);
   PGA_HIP_CHECK(hipGetLastError());
 }
 

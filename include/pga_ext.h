@@ -70,8 +70,14 @@ int pga_set_rank_pressure(pga_t *p, population_t *pop, float sp);
  * pga_local_search runs the stage once on the current population with the
  * values set here (moves 1, prob 1 by default), also with kind NONE; the
  * generation counter does not advance, and a second call in the same
- * generation selects the same individuals. */
-enum pga_local_search { PGA_LS_NONE = 0, PGA_LS_TWO_OPT = 1 };
+ * generation selects the same individuals.
+ * PGA_LS_ONE_FLIP is the same stage for BINARY populations with the built-in
+ * QUBO objective (PGA_OBJ_QUBO, Max-Cut included): each move flips the single
+ * bit with the largest gain in score, ties to the lowest position, and a row
+ * stops when no flip gains; Q need not be symmetric; exact integer arithmetic.
+ * pga_local_search picks the stage by the population: 2-opt for PERMUTATION,
+ * one-flip for BINARY with QUBO. */
+enum pga_local_search { PGA_LS_NONE = 0, PGA_LS_TWO_OPT = 1, PGA_LS_ONE_FLIP = 2 };
 int pga_set_local_search(pga_t *p, population_t *pop, enum pga_local_search kind, unsigned moves, float prob);
 int pga_local_search(pga_t *p, population_t *pop);
 

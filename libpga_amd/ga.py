@@ -33,7 +33,8 @@ MUTATIONS = {
     "swap": C.MUT_SWAP, "inversion": C.MUT_INVERSION, "none": C.MUT_NONE,
 }
 
-LOCAL_SEARCHES = {None: C.LS_NONE, "none": C.LS_NONE, "two_opt": C.LS_TWO_OPT}
+LOCAL_SEARCHES = {None: C.LS_NONE, "none": C.LS_NONE, "two_opt": C.LS_TWO_OPT,
+                  "one_flip": C.LS_ONE_FLIP}
 
 
 def default_device() -> torch.device:
@@ -92,7 +93,7 @@ class GeneticAlgorithm:
         # the objective the Python layer evaluates (None: native, fused or JIT)
         self.torch_objective = problem.torch_objective
         if ops.local_search not in (None, "none") and self.torch_objective is not None:
-            raise ValueError("local search needs a native TSP objective, not a torch objective")
+            raise ValueError("local search needs a native TSP or QUBO objective, not a torch objective")
         if getattr(problem, "jit_source", None) is not None:
             if self.device.type == "cuda":
                 self._island.set_jit_objective(problem.kernel())
@@ -117,7 +118,7 @@ class GeneticAlgorithm:
         cfg.rank_pressure = float(ops.rank_pressure)
         cfg.n_elite = int(ops.elitism)
         if ops.local_search not in LOCAL_SEARCHES:
-            raise ValueError(f"unknown local search {ops.local_search!r} (None or 'two_opt')")
+            raise ValueError(f"unknown local search {ops.local_search!r} (None, 'two_opt' or 'one_flip')")
         cfg.local_search = LOCAL_SEARCHES[ops.local_search]
         cfg.ls_moves = int(ops.ls_moves)
         cfg.ls_prob = float(ops.ls_prob)
@@ -164,17 +165,20 @@ class GeneticAlgorithm:
             self._island.evaluate()
 
     def local_search(self, moves: Optional[int] = None, prob: Optional[float] = None) -> None:
-        """One 2-opt local search stage on the current population, in place:
-        up to ``moves`` best-improvement moves on each individual selected
-        with probability ``prob`` (defaults: the operators' ``ls_moves`` /
+        """One local search stage on the current population, in place: up to
+        ``moves`` best-improvement moves on each individual selected with
+        probability ``prob`` (defaults: the operators' ``ls_moves`` /
         ``ls_prob``).  PERMUTATION with a native TSP objective (a symmetric
-        matrix, or coordinates).  No tour gets longer; rows that moved are
+        matrix, or coordinates): 2-opt moves.  BINARY with the native QUBO
+        objective (``QUBO``, ``MaxCut``; Q need not be symmetric): single-bit
+        flips, the largest gain first, ties to the lowest bit, in exact
+        integer arithmetic.  No score gets worse; rows that moved are
         rescored, the others are untouched.  The generation counter does not
         advance, and the selection is a function of (seed, generation,
         individual): calling the stage twice in one generation selects the
         same individuals."""
         if self.torch_objective is not None:
-            raise ValueError("local search needs a native TSP objective, not a torch objective")
+            raise ValueError("local search needs a native TSP or QUBO objective, not a torch objective")
         m = self.operators.ls_moves if moves is None else moves
         p = self.operators.ls_prob if prob is None else prob
         if int(m) < 0:
