@@ -391,6 +391,14 @@ __global__ __launch_bounds__(kBlock) void binary_kernel(GenArgs a, unsigned long
 //                32-byte child RECORD in the wave's LDS ring (2 batches);
 //                per step: XO mask Philox (one block per chunk), mix, flips,
 //                popcount, group butterfly, stores.
+//                Two loop forms (BREED below): the rotating three-set loop
+//                with per-step score / key stores, and for the exact-key
+//                objectives at GS 4 / 8 and full units the UNIT loop: GS
+//                straight-line steps over four register sets, static
+//                cursors, the scores transposed to one child per lane and
+//                ONE epilogue per unit, and a wait for the next step's rows
+//                before each step's arithmetic (-2.4 us at the headline;
+//                115 VGPRs, 106 SGPRs, scratch 0).
 // Why two phases: the EA (L2 -> fabric) traffic is the bound (PMC: ~530 MB
 // per generation at 1M x 1024 bits, ~5.7 TB/s).  Tournament keys are a 2 MB
 // array read at random; interleaved with the row gathers, ~1/4 of the key
@@ -407,8 +415,13 @@ __global__ __launch_bounds__(kBlock) void binary_kernel(GenArgs a, unsigned long
 
 #ifdef PGA_TP_TIMING
 // experiment builds only (tools/variants.sh): per-wave clocks of the two
-// phases, wall-clock start / end and the XCD the wave ran on
-__device__ unsigned long long pga_tp_clk[kMaxGrid * 4][8];
+// phases, wall-clock start / end, the XCD the wave ran on, and its waits at
+// the FIRST round's first barrier (launch skew inside the block: on the
+// critical path), at the later rounds' first barriers (they follow the
+// previous round's last barrier at once) and at the rounds' last barriers (the
+// block's tail: not on the critical path)
+constexpr uint32_t kTpClkWords = 11;
+__device__ unsigned long long pga_tp_clk[kMaxGrid * 4][kTpClkWords];
 #endif
 
 // kTpMaxElite (elites the fast kernel routes through its records),
@@ -453,6 +466,11 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
   // block writes, after the round's parents in dynamic LDS (the launcher adds
   // hist_bins words), flushed with one global atomic per non-empty bin
   constexpr bool HISTK = KEY && !JIT;
+  // the breed loop unrolled per 64-child unit with the per-unit epilogue
+  // (BREED below): the exact-key objectives at the group sizes whose unit (GS
+  // steps, four register sets at PD = 2) unrolls into the instruction cache --
+  // 16 steps are ~68 KB of code, and a partly unrolled unit measured slower
+  constexpr bool UNITF = HISTK && PD == 2 && (GS == 4 || GS == 8);
 
   const uint32_t lane = lane_id(), wid = threadIdx.x >> 6;
   const uint32_t q = lane & (GS - 1), gbase = lane & ~(uint32_t)(GS - 1), g = lane / GS;
@@ -516,15 +534,20 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
   static_assert(sizeof(lds_rec[0]) >= kSegBatches * 64 * sizeof(uint4), "contestant staging");
 #ifdef PGA_TP_TIMING
   const unsigned long long clk0 = clock64(), rt0 = wall_clock64();
-  unsigned long long clk_t = 0, clk_b = 0, n_bred = 0, clk_spin = 0;
+  unsigned long long clk_t = 0, clk_b = 0, n_bred = 0, clk_spin = 0, clk_sync0 = 0, clk_syncn = 0, clk_sync1 = 0;
 #endif
   for (uint32_t rbeg = bbegin; rbeg < bend; rbeg += pcap) {  // block-uniform rounds
     const uint32_t rend = rbeg + pcap < bend ? rbeg + pcap : bend;  // the round's children
     const uint32_t nu = (rend - rbeg + U - 1) / U;                  // its units: U children each
     const uint32_t nseg = (rend - rbeg + kSegBatches * 64 - 1) / (kSegBatches * 64);  // its tournament segments
+#ifdef PGA_TP_TIMING
+    const unsigned long long clkS = clock64();
+#endif
     __syncthreads();  // tables / counters visible; the previous round's records and parents released
 #ifdef PGA_TP_TIMING
     const unsigned long long clkA = clock64();
+    if (rbeg == bbegin) clk_sync0 += clkA - clkS;
+    else clk_syncn += clkA - clkS;
 #endif
     if (rbeg == bbegin && wid == 0) {  // wave-uniform: the prologue loads (lds_pro)
       if (a.n_elite > 0 && bbegin < a.n_elite) {
@@ -676,8 +699,8 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
       uint32_t slot = 0, i = 0, bs = ns, be = ne;
       PGA_TP_NEXT(ns, ne)
       PGA_TP_RESOLVE(bs, be, 0u)
-      // load cursor; lpend: at the end of its unit with unit ns next;
-      // lmore = false: past the wave's last step
+      // load cursor of the rotating loop; lpend: at the end of its unit with
+      // unit ns next; lmore = false: past the wave's last step
       uint32_t lslot = 0, li = 0, lbs = bs, lbe = be;
       bool lpend = false, lmore = true, done = false;
 
@@ -703,14 +726,14 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
     }                                                                                                       \
   }
 
-      // one STEP: load PD steps ahead into (YA, YB), breed the breed cursor's
-      // step i from (XA, XB) (its children past S, at the population's end
-      // only, write the padding rows), advance the breed cursor
-#define PGA_TP_STEP(XA, XB, YA, YB)                                                                         \
-  {                                                                                                         \
-    PGA_TP_LOAD(YA, YB)                                                                                     \
-    const uint32_t c = bs + i * NG + g;                                                                     \
-    const uint4 r0 = rec[slot][i * NG + g][0];                                                              \
+      // BREED step I of the breed cursor's unit from the parent rows (XA, XB):
+      // child c = bs + I * NG + g, its row v stored, its score sc (uniform
+      // over the group's lanes; JIT: evaluated later).  Children past S, at
+      // the population's end only, write the padding rows.  Shared by the two
+      // loop forms; c, v and sc stay in the enclosing scope.
+#define PGA_TP_BREED(XA, XB, I)                                                                             \
+    const uint32_t c = bs + (I) * NG + g;                                                                   \
+    const uint4 r0 = rec[slot][(I) * NG + g][0];                                                            \
     const uint32_t meta = r0.w;                                                                             \
     const uint4 m = range ? range_keep_a(q, r0.z & 0xFFFFu, r0.z >> 16) : u4(draw<true>(a.key, ST_XO, c, q)); \
     uint4 v = mix4(XA, XB, m);                                                                              \
@@ -722,7 +745,7 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
     } else {                                                                                                \
       const uint32_t K = meta & 0xFFu;                                                                      \
       if (K > 0u) {                                                                                         \
-        const uint4 r1 = rec[slot][i * NG + g][1];                                                          \
+        const uint4 r1 = rec[slot][(I) * NG + g][1];                                                        \
         const uint32_t kk = K < kRecPos ? K : kRecPos;                                                      \
         /* the first 4 unrolled (a loop here costs ~20 VGPRs of the whole kernel) */                       \
         _Pragma("unroll") for (uint32_t k = 0; k < 4; ++k) {                                               \
@@ -748,12 +771,12 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
       if (have) acc.add(a, v, q);                                                                           \
       sc = acc.template finish<GS>(a);                                                                      \
     }                                                                                                       \
-    if (have) ROW(nxt, c, q) = v;                                                                           \
-    if constexpr (JIT) {                                                                                    \
-      lds_stage[(i % kJitStageSteps) * 64u + lane] = v;                                                     \
-      if (i % kJitStageSteps == kJitStageSteps - 1u || i + 1u == nst) PGA_TP_JIT_EVAL                       \
-    }                                                                                                       \
-    if (EVALS && !JIT) { /* every lane of the group stores the same score */                                \
+    if (have) ROW(nxt, c, q) = v;
+
+      // the per-STEP epilogue of child c: every lane of the group stores the
+      // same score
+#define PGA_TP_STEP_SCORE                                                                                   \
+    if (EVALS && !JIT) {                                                                                    \
       ELEM(float, a.score_next, c) = sc;                                                                    \
       if (KEY) ELEM(uint16_t, a.key_next, c) = (uint16_t)sc;                                                \
       if (hist && q == 0u && c < S) {                                                                       \
@@ -764,7 +787,19 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
       const unsigned long long pk = c < S ? pack_best(sc, c) : 0ull;                                        \
       my_best = pk > my_best ? pk : my_best;                                                                \
       st.add_if(q == 0u && c < S, sc);                                                                      \
+    }
+
+      // one STEP of the rotating loop: load PD steps ahead into (YA, YB), breed
+      // the breed cursor's step i from (XA, XB), advance the breed cursor
+#define PGA_TP_STEP(XA, XB, YA, YB)                                                                         \
+  {                                                                                                         \
+    PGA_TP_LOAD(YA, YB)                                                                                     \
+    PGA_TP_BREED(XA, XB, i)                                                                                 \
+    if constexpr (JIT) {                                                                                    \
+      lds_stage[(i % kJitStageSteps) * 64u + lane] = v;                                                     \
+      if (i % kJitStageSteps == kJitStageSteps - 1u || i + 1u == nst) PGA_TP_JIT_EVAL                       \
     }                                                                                                       \
+    PGA_TP_STEP_SCORE                                                                                       \
     if (++i == nst) {                                                                                       \
       PGA_TP_COUNT                                                                                          \
       if (lbs == bs) { /* the load cursor never left this unit: it was the wave's last */                   \
@@ -803,9 +838,104 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
 #define PGA_TP_COUNT
 #endif
 
-      uint4 A0, B0, A1, B1, A2, B2, A3, B3;  // PD + 1 register sets, rotated statically
+      // one step I of the UNIT loop (full units: GS steps, the load cursor a
+      // static PD steps ahead; the exact-key objectives only, UNITF): the loads
+      // of step I + PD into (YA, YB) -- from step GS - PD on in the wave's next
+      // unit, RESOLVEd into the other ring slot there, once; a wave without
+      // one re-reads its own step's rows -- then breed step I from (XA, XB)
+      // and move the group's score to lane I * NG + group (one ds_bpermute and
+      // a select); nothing but the row is stored per step.
+      // Before the arithmetic the step waits until the rows of step I + 1
+      // (NA, NB) have landed too (an empty asm reads them): while a wave
+      // computes, one pair of row loads is in flight, not two.  The fabric is
+      // the bound, and holding the second pair back measured 2.4 us per
+      // generation faster at the headline (docs/ARCHITECTURE.md, section 4).
+#define PGA_TP_USTEP(I, XA, XB, YA, YB, NA, NB)                                                             \
+  {                                                                                                         \
+    const uint32_t ul_ = (I) + PD;                                                                          \
+    if (ul_ == (uint32_t)GS) { /* wave-uniform; no vector memory operation inside */                        \
+      hn = ns != kNoUnit;                                                                                   \
+      if (hn) {                                                                                             \
+        PGA_TP_RESOLVE(ns, ne, slot ^ 1u)                                                                   \
+        nbs = ns;                                                                                           \
+        nbe = ne;                                                                                           \
+        PGA_TP_NEXT(ns, ne)                                                                                 \
+      }                                                                                                     \
+    }                                                                                                       \
+    const bool un_ = ul_ >= (uint32_t)GS;                                                                   \
+    const uint4 ur_ = rec[un_ && hn ? slot ^ 1u : slot][(un_ ? (hn ? ul_ - GS : (I)) : ul_) * NG + g][0];   \
+    YA = ROW(cur, ur_.x, qq);                                                                               \
+    YB = ROW(cur, ur_.y, qq);                                                                               \
+    {                                                                                                       \
+      const uint32_t w_ = NA.x | NB.x;                                                                      \
+      asm volatile("" ::"v"(w_));                                                                           \
+    }                                                                                                       \
+    PGA_TP_BREED(XA, XB, I)                                                                                 \
+    const float t_ = __shfl(sc, (int)usrc, 64);                                                             \
+    usc = lane / NG == (I) ? t_ : usc;                                                                      \
+  }
+
+      uint4 A0, B0, A1, B1, A2, B2, A3, B3;  // PD + 1 register sets, rotated statically (the unit loop: 4)
       (void)A2; (void)B2; (void)A3; (void)B3;
-      if constexpr (PD == 1) {
+      if (UNITF && U == 64u) {  // full units of GS steps (wave-uniform)
+        // the unit's scores, one child per lane (child bs + lane), gathered
+        // step by step from lane usrc, a lane of group lane % NG
+        float usc = 0.f;
+        const uint32_t usrc = (lane % NG) * GS + lane / NG;
+        // hn: the wave has a next unit [nbs, nbe), known once the load cursor
+        // has left the current one
+        bool hn = false;
+        uint32_t nbs = 0, nbe = 0;
+        {
+          const uint4 r = rec[0][g][0];
+          A0 = ROW(cur, r.x, qq);
+          B0 = ROW(cur, r.y, qq);
+        }
+        {
+          const uint4 r = rec[0][NG + g][0];
+          A1 = ROW(cur, r.x, qq);
+          B1 = ROW(cur, r.y, qq);
+        }
+        for (;;) {
+#pragma unroll
+          for (uint32_t u = 0; u < (uint32_t)GS; u += 4u) {  // one rotation of the four register sets
+            PGA_TP_USTEP(u, A0, B0, A2, B2, A1, B1)
+            PGA_TP_USTEP(u + 1u, A1, B1, A3, B3, A2, B2)
+            PGA_TP_USTEP(u + 2u, A2, B2, A0, B0, A3, B3)
+            PGA_TP_USTEP(u + 3u, A3, B3, A1, B1, A0, B0)
+          }
+          // The unit's epilogue, once per child: lane j holds the score of
+          // child bs + j.  Statistics: every lane now adds one child per unit
+          // where lane q == 0 of a group added GS.  The scores are
+          // non-negative integers (exact keys, <= 65535), so every per-lane,
+          // per-wave and per-block partial sum is bounded by the block's
+          // total; while that is below 2^24 all of them are exact in f32 and
+          // the block's {min, sum} equals the rotating loop's bit for bit.
+          // Above it (a block share x mean score >= 2^24: from S ~ 8 M at
+          // L = 1024 on 256 CUs) the rotating loop's sum already depends on
+          // which wave pulled which unit, i.e. it differs from run to run;
+          // the launcher's users that need exact sums check the same bound
+          // (roulette_fused_launch).
+          {
+            const uint32_t c = bs + lane;
+            ELEM(float, a.score_next, c) = usc;
+            ELEM(uint16_t, a.key_next, c) = (uint16_t)usc;
+            if (hist && c < S) {
+              const uint32_t kb = (uint16_t)usc;
+              __hip_atomic_fetch_add(&lds_hist[kb < hmax ? kb : hmax], 1u, __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            const unsigned long long pk = c < S ? pack_best(usc, c) : 0ull;
+            my_best = pk > my_best ? pk : my_best;
+            st.add_if(c < S, usc);
+          }
+          PGA_TP_COUNT
+          if (!hn) break;  // the load cursor never left this unit: it was the wave's last
+          slot ^= 1u;
+          bs = nbs;
+          be = nbe;
+        }
+      } else if constexpr (PD == 1) {
         PGA_TP_LOAD(A0, B0)
         for (;;) {
           PGA_TP_STEP(A0, B0, A1, B1)
@@ -839,7 +969,10 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
           if (done) break;
         }
       }
+#undef PGA_TP_USTEP
 #undef PGA_TP_STEP
+#undef PGA_TP_STEP_SCORE
+#undef PGA_TP_BREED
 #undef PGA_TP_LOAD
 #undef PGA_TP_NEXT
 #undef PGA_TP_JIT_EVAL
@@ -850,9 +983,13 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
 #undef PGA_TP_SPIN1
 #ifdef PGA_TP_TIMING
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this round's stores issued and done
-    clk_b += clock64() - clkB;
+    const unsigned long long clkE = clock64();
+    clk_b += clkE - clkB;
 #endif
     __syncthreads();  // every wave out of the round's counters before they are reset
+#ifdef PGA_TP_TIMING
+    clk_sync1 += clock64() - clkE;
+#endif
     if (threadIdx.x == 0) lds_next = lds_tnext = 0;
     if (threadIdx.x < kTpMaxSegs) lds_ready[threadIdx.x] = 0;
   }
@@ -869,6 +1006,9 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
     pga_tp_clk[wv][5] = wall_clock64();
     pga_tp_clk[wv][6] = __builtin_amdgcn_s_getreg((3 << 11) | 20);  // HW_REG_XCC_ID[3:0]
     pga_tp_clk[wv][7] = clk_spin;  // cycles a breeding wave waited for a segment's flag
+    pga_tp_clk[wv][8] = clk_sync0;   // ... at the first round's first barrier
+    pga_tp_clk[wv][9] = clk_sync1;   // ... at the rounds' last barriers
+    pga_tp_clk[wv][10] = clk_syncn;  // ... at the later rounds' first barriers
   }
 #endif
   if (hist)  // every wave passed the last round's barrier: the block's counts are complete

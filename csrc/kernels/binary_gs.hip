@@ -127,9 +127,9 @@ uint32_t binary_launch_group<PGA_BIN_GS>(int mode, const GenArgs& a, unsigned lo
 // experiment builds: mean per-wave cycles of the tournament / breed phases of
 // the last binary_gen_tp launch (bench/gen_bench.cpp prints it)
 extern "C" void pga_tp_timing_dump(uint32_t nwaves) {
-  static unsigned long long h[kMaxGrid * 4][8];  // per wave: blockIdx.x * waves + wave
+  static unsigned long long h[kMaxGrid * 4][kTpClkWords];  // per wave: blockIdx.x * waves + wave
   PGA_HIP_CHECK(hipMemcpyFromSymbol(h, HIP_SYMBOL(pga_tp_clk), sizeof(h)));
-  double t = 0, b = 0, tot = 0, n = 0, mx = 0;
+  double t = 0, b = 0, tot = 0, n = 0, mx = 0, s0 = 0, sn = 0, s1 = 0;
   unsigned long long rt_min = ~0ull, rt_max = 0, st_max = 0;
   uint32_t nw = 0;
   for (uint32_t i = 0; i < nwaves && i < kMaxGrid * 4; ++i) {
@@ -137,6 +137,9 @@ extern "C" void pga_tp_timing_dump(uint32_t nwaves) {
     t += (double)h[i][0];
     b += (double)h[i][1];
     tot += (double)h[i][2];
+    s0 += (double)h[i][8];
+    s1 += (double)h[i][9];
+    sn += (double)h[i][10];
     mx = std::max(mx, (double)h[i][2]);
     n += 1;
     rt_min = std::min(rt_min, h[i][4]);
@@ -145,9 +148,12 @@ extern "C" void pga_tp_timing_dump(uint32_t nwaves) {
     nw = i + 1;
   }
   std::printf("{\"tp_timing\": {\"waves\": %.0f, \"tourn_cycles\": %.0f, \"breed_cycles\": %.0f, "
+              "\"first_barrier_cycles\": %.0f, \"later_first_barrier_cycles\": %.0f, "
+              "\"last_barrier_cycles\": %.0f, "
               "\"wave_cycles\": %.0f, \"max_wave_cycles\": %.0f, \"tourn_frac\": %.3f, "
               "\"span_us\": %.2f, \"last_start_us\": %.2f}}\n",
-              n, t / n, b / n, tot / n, mx, t / (t + b), (rt_max - rt_min) / 100.0, (st_max - rt_min) / 100.0);
+              n, t / n, b / n, s0 / n, sn / n, s1 / n, tot / n, mx, t / (t + b), (rt_max - rt_min) / 100.0,
+              (st_max - rt_min) / 100.0);
   // wall-clock end time (us after the first start, 100 MHz clock) per XCD and
   // by block order (older blocks first): is the tail an XCD or an age effect?
   double xe[8] = {0}, xm[8] = {0}, xn[8] = {0};
