@@ -929,6 +929,15 @@ std::vector<uint32_t> Island::row_host(uint64_t i) {
   return out;
 }
 
+bool Island::qkeys_host(int which, std::vector<uint16_t>& keys, float range[2]) {
+  const int p = (which & 1) ^ cur_;
+  if (!real_qk() || !qk_valid_[p] || !qk_ws_.ptr || !keys_[p].ptr) return false;
+  keys.resize(cfg_.S);
+  copy_to_host(keys.data(), keys_[p].ptr, 2ull * cfg_.S);
+  copy_to_host(range, qk_ws_.ptr, 8);
+  return true;
+}
+
 void Island::gather(const uint32_t* idx, uint32_t n, void* out_rows, float* out_scores) {
   TraceRange tr("pga.migrate.gather");
   if (on_gpu())

@@ -153,6 +153,12 @@ class Island {
   std::vector<float> history();
   std::vector<uint32_t> topk_host(uint32_t k, bool largest);
   std::vector<uint32_t> row_host(uint64_t i);
+  // read-only view of the REAL quantized tournament keys (tests): host copies
+  // of the u16 keys of parity `which` (the convention of rows(which)) and of
+  // the range {min, max} they were last refreshed to.  false when this island
+  // keeps no such keys or those of that parity are not valid.  Launches
+  // nothing and changes no state (the refresh age included).
+  bool qkeys_host(int which, std::vector<uint16_t>& keys, float range[2]);
 
   // ---- device-side building blocks (no sync) ----
   // idx_out: device (or host for CPU) memory.  sorted: best first (ties by
@@ -240,9 +246,14 @@ class Island {
   Buffer rank_order_, rank_ws_;
   Buffer roul_guide_;  // roulette guide table (GPU), S + 1 entries
   // REAL on the GPU: quantized u16 tournament keys in keys_[p] (qkey), valid
-  // when qk_valid_[p]; qk_ws_ = {min, max, sum, count} of the current
-  // generation (+ score_stats workspace), the range the GEN kernel quantizes
-  // the next generation's keys over
+  // when qk_valid_[p]: written by the GEN kernel that bred parity p, or by
+  // prepare_generation() after anything else rewrote its scores.  qk_ws_ =
+  // {min, max, sum, count} (+ score_stats workspace) of the scores of the
+  // generation of the last refresh (every 8 or 32 generations, qk_age_), NOT
+  // of the current one: the range the GEN kernel quantizes the next
+  // generation's keys over, and prepare_generation() a re-keyed current one.
+  // All keys of ONE parity share a range; the two parities' ranges differ
+  // across a refresh (only keys of one parity are ever compared).
   bool real_qk() const;
   void invalidate_qk() {
     qk_valid_[cur_] = false;

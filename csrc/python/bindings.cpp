@@ -273,6 +273,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              return view(i, i->scores(which), {(int64_t)i->config().S}, torch::kFloat32);
            },
            py::arg("which") = 0)
+      // (keys [S] int32, range [2] float32) host copies of the REAL quantized
+      // tournament keys of that parity and their range, or None when the island
+      // keeps none / they are not valid (Island::qkeys_host; read-only, tests)
+      .def("qkeys",
+           [](Island& i, int which) -> py::object {
+             bind_stream(i);
+             std::vector<uint16_t> k;
+             float r[2];
+             if (!i.qkeys_host(which, k, r)) return py::none();
+             auto keys = torch::empty({(int64_t)k.size()}, torch::dtype(torch::kInt32));
+             int32_t* o = keys.data_ptr<int32_t>();
+             for (size_t j = 0; j < k.size(); ++j) o[j] = (int32_t)k[j];
+             auto range = torch::empty({2}, torch::dtype(torch::kFloat32));
+             std::memcpy(range.data_ptr<float>(), r, 8);
+             return py::make_tuple(keys, range);
+           },
+           py::arg("which") = 0)
       .def("best_parts",
            [](const IslandPtr& i) { return view(i, i->best_parts(), {(int64_t)pga::kMaxGrid}, torch::kInt64); })
       .def_property("n_best", &Island::n_best, &Island::set_n_best)
