@@ -671,6 +671,7 @@ void Island::run_plain(uint32_t n) {
     if (a.rank_counts) a.hist_bins = cfg_.L + 1;
     n_best_[cur_ ^ 1] = launch(MODE_GEN, a, (unsigned long long*)best_[cur_ ^ 1].ptr);
     set_stats_ok(cur_ ^ 1, a.stats_parts != nullptr);
+    tp_tail_ = cfg_.encoding == ENC_BINARY && on_gpu() ? binary_tp_partition().tail : 0u;
     if (a.stats_parts && cfg_.encoding == ENC_BINARY && on_gpu() && binary_tp_partition().grid == n_best_[cur_ ^ 1])
       stats_part_[cur_ ^ 1] = binary_tp_partition();  // (the roulette prefix's carries, roulette_fused_launch)
     rank_cnt_of_ = a.rank_counts && binary_rank_counts_written() ? (cur_ ^ 1) : -1;
@@ -776,6 +777,7 @@ bool Island::run_batched(const std::vector<Island*>& isls, uint32_t n, hipStream
       I.qk_valid_[nx] = real && args[k].qk != nullptr;  // the REAL kernel writes the keys it is given
       I.fhist_of_[nx] = -1;  // the batched launch produces no fused histogram
       I.rank_cnt_of_ = -1;
+      I.tp_tail_ = bin ? binary_tp_partition().tail : 0u;
       I.swap();
     }
   }

@@ -397,8 +397,20 @@ __global__ __launch_bounds__(kBlock) void binary_kernel(GenArgs a, unsigned long
 //                straight-line steps over four register sets, static
 //                cursors, the scores transposed to one child per lane and
 //                ONE epilogue per unit, and a wait for the next step's rows
-//                before each step's arithmetic (-2.4 us at the headline;
-//                115 VGPRs, 106 SGPRs, scratch 0).
+//                before each step's arithmetic (-2.4 us at the headline).
+//                TAIL (the GS 8 unit loop on the 16-wave launch): the last
+//                GenArgs::tp_tail units of a round are owned by no wave.  The
+//                wave that draws such a unit's ticket RESOLVEs it into
+//                block-shared records behind the histogram bins and sets the
+//                unit's flag; waves without an owned unit left pull the tail's
+//                STEPS (NG children each) from a third counter, with the
+//                rotating loop's three register sets, the same wait and the
+//                per-step epilogue, and a wave leaves its last owned unit
+//                with its first two tail steps' rows already in flight.  The
+//                waves of a block then end within a step of each other
+//                instead of within a unit (last-barrier wait 9.5 K -> 2.2 K
+//                cycles; profiles/tail_steps.md).  125 VGPRs, 104 SGPRs,
+//                scratch 0.
 // Why two phases: the EA (L2 -> fabric) traffic is the bound (PMC: ~530 MB
 // per generation at 1M x 1024 bits, ~5.7 TB/s).  Tournament keys are a 2 MB
 // array read at random; interleaved with the row gathers, ~1/4 of the key
@@ -420,7 +432,7 @@ __global__ __launch_bounds__(kBlock) void binary_kernel(GenArgs a, unsigned long
 // critical path), at the later rounds' first barriers (they follow the
 // previous round's last barrier at once) and at the rounds' last barriers (the
 // block's tail: not on the critical path)
-constexpr uint32_t kTpClkWords = 11;
+constexpr uint32_t kTpClkWords = 14;
 __device__ unsigned long long pga_tp_clk[kMaxGrid * 4][kTpClkWords];
 #endif
 
@@ -451,6 +463,10 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
   __shared__ uint32_t lds_next;   // the round's next unbred unit
   __shared__ uint32_t lds_tnext;  // the round's next tournament segment
   __shared__ uint32_t lds_ready[kTpMaxSegs];  // per segment: its parents are in LDS
+  // tail steps (TAIL below; the unit loop on the 16-wave launch only): the
+  // round's next tail step, and per tail unit: its records are in LDS
+  __shared__ uint32_t lds_tstep;
+  __shared__ uint32_t lds_tready[kTpMaxTail];
   constexpr bool KMF = OBJ == kObjKnapMfma;
   __shared__ uint4 lds_kscr[KMF ? kTpMaxWaves : 1][kKnapScratch];      // knapsack: per-wave chunk / C scratch
   __shared__ uint4 lds_ktab[KMF ? kKnapSlices * 4 * kKnapMaxCols : 1];  // knapsack: digit table
@@ -471,6 +487,10 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
   // steps, four register sets at PD = 2) unrolls into the instruction cache --
   // 16 steps are ~68 KB of code, and a partly unrolled unit measured slower
   constexpr bool UNITF = HISTK && PD == 2 && (GS == 4 || GS == 8);
+  // the unit loop's TAIL steps (BREED below), at GS 8 only: at GS 4 (steps of 16
+  // children, 4 per unit) they measured 0.3 us SLOWER at OneMax-512
+  // (profiles/tail_steps_ab.txt), so those kernels compile without them
+  constexpr bool TAILF = UNITF && GS == 8;
 
   const uint32_t lane = lane_id(), wid = threadIdx.x >> 6;
   const uint32_t q = lane & (GS - 1), gbase = lane & ~(uint32_t)(GS - 1), g = lane / GS;
@@ -521,6 +541,10 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
       lds_ktab[i] = ((const uint4*)a.knap_tab)[i];
   if (threadIdx.x == 0) lds_next = lds_tnext = lds_pro = 0;
   if (threadIdx.x < kTpMaxSegs) lds_ready[threadIdx.x] = 0;
+  if constexpr (TAILF) {
+    if (threadIdx.x == 0) lds_tstep = 0;
+    if (threadIdx.x < kTpMaxTail) lds_tready[threadIdx.x] = 0;
+  }
   if (hist) {
     for (uint32_t i = threadIdx.x; i < a.hist_bins; i += blockDim.x) lds_hist[i] = 0;
     if (a.hist_zero)  // a later generation's histogram starts from zero
@@ -535,6 +559,7 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
 #ifdef PGA_TP_TIMING
   const unsigned long long clk0 = clock64(), rt0 = wall_clock64();
   unsigned long long clk_t = 0, clk_b = 0, n_bred = 0, clk_spin = 0, clk_sync0 = 0, clk_syncn = 0, clk_sync1 = 0;
+  unsigned long long clk_tail = 0, n_tail = 0, clk_tflag = 0;  // the tail loop: cycles, steps bred, waits on unit flags
 #endif
   for (uint32_t rbeg = bbegin; rbeg < bend; rbeg += pcap) {  // block-uniform rounds
     const uint32_t rend = rbeg + pcap < bend ? rbeg + pcap : bend;  // the round's children
@@ -550,16 +575,18 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
     else clk_syncn += clkA - clkS;
 #endif
     if (rbeg == bbegin && wid == 0) {  // wave-uniform: the prologue loads (lds_pro)
+      uint32_t plane = lane;  // (the unit loop's kernels: opaque, as at the kernel's end)
+      if constexpr (TAILF) asm volatile("" : "+v"(plane));
       if (a.n_elite > 0 && bbegin < a.n_elite) {
         if (a.elite_idx) {
-          for (uint32_t i = lane; i < a.n_elite; i += 64) lds_el[i] = a.elite_idx[i];
+          for (uint32_t i = plane; i < a.n_elite; i += 64) lds_el[i] = a.elite_idx[i];
         } else {
           const unsigned long long b = wave_reduce_parts(a.best_cur, a.n_best_cur);
           if (lane == 0) lds_el[0] = (uint32_t)best_index(b);
         }
       }
       if (bitflip)
-        for (uint32_t i = lane; i < kMutCap; i += 64) lds_thr[i] = a.mut_thr[i];
+        for (uint32_t i = plane; i < kMutCap; i += 64) lds_thr[i] = a.mut_thr[i];
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
       tp_flag_set(&lds_pro);
     }
@@ -602,7 +629,7 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
 #endif
     // RESOLVE: parents, crossover plan and flip positions of the round's unit
     // BI -> the records of ring slot SL (lanes past the unit: unused copies)
-#define PGA_TP_RESOLVE(US, UE, SL)                                                                              \
+#define PGA_TP_RESOLVE_TO(US, UE, DST)                                                                         \
   {                                                                                                             \
     if (!pro_ok) { /* the prologue loads of wave 0 (once per wave) */                                          \
       while (__hip_atomic_load(&lds_pro, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u)                 \
@@ -660,10 +687,11 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
       }                                                                                                         \
     }                                                                                                           \
     const uint32_t meta = (K > 255u ? 255u : K) | ((jn > 0xFFFFu ? 0xFFFFu : jn) << 8) | (elite ? 1u << 31 : 0u); \
-    uint4(*r)[2] = rec[(SL)];                                                                                   \
+    uint4(*r)[2] = (DST);                                                                                       \
     r[lane][0] = make_uint4(pa, pb, lo | (hi << 16), meta);                                                     \
     r[lane][1] = P;                                                                                             \
   }
+#define PGA_TP_RESOLVE(US, UE, SL) PGA_TP_RESOLVE_TO(US, UE, rec[(SL)])
 
     // BREED: the round's units in ticket order from the block's counter, as
     // two cursors over the wave's sequence of steps: the LOAD cursor issues
@@ -677,28 +705,117 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
     // conditionally issued load would make the next wait drain it): an
     // exhausted load cursor re-reads the breed cursor's rows.
     // NEXT unit [US, UE) of this wave (US = kNoUnit: none), from the block's
-    // LDS counter
+    // LDS counter.  Tickets [nown, nu) are the round's TAIL units (below): the
+    // wave that draws one owes its RESOLVE (tpend) and owns none of its steps
     constexpr uint32_t kNoUnit = 0xFFFFFFFFu;
+    // TAIL: the last tcap units of a round (nu - nown of them, ntst steps in
+    // all; none: nown = nu) are bred step by step by whichever wave is free;
+    // their records are block-shared, 2 KB per unit after the histogram bins
+    // (the launcher sizes the launch for tp_tail units).  Worked out here, not
+    // at the kernel's start: nothing of it is live across the tournaments
+    const uint32_t tcap = TAILF && U == 64u && NW == kTpMaxWaves ? (a.tp_tail < kTpMaxTail ? a.tp_tail : kTpMaxTail) : 0u;
+    const uint32_t nown = nu - (tcap < nu ? tcap : nu), ntst = (nu - nown) * (uint32_t)GS;
+    const uint32_t toff = tp_tail_off(NW * 4096u + pcap * 8u + (hist ? 4u * a.hist_bins : 0u));
+    uint4(*trec)[64][2] = (uint4(*)[64][2])(pga_dyn_lds + toff);
+    (void)trec;
+    uint32_t tpend = kNoUnit;  // the tail unit this wave drew and has not resolved yet
+    (void)tpend;
 #define PGA_TP_NEXT(US, UE)                                                                                 \
   {                                                                                                         \
     US = kNoUnit;                                                                                           \
     const uint32_t tk_ = tp_ticket(&lds_next, lane);                                                        \
-    if (tk_ < nu) {                                                                                         \
+    if (tk_ < nown) {                                                                                       \
       US = rbeg + tk_ * U;                                                                                  \
       UE = US + U < rend ? US + U : rend;                                                                   \
+    } else if (TAILF && tk_ < nu) {                                                                         \
+      tpend = tk_ - nown;                                                                                   \
     }                                                                                                       \
   }
 
+    // TAIL (the GS 8 unit loop on the 16-wave launch, GenArgs::tp_tail > 0).  The
+    // unit counter levels the block's waves only to within one unit (~28 K
+    // cycles of a wave's ~114 K breed cycles at the headline), and a wave that
+    // is done idles until the block's last barrier.  So the last ntst / GS
+    // units of the round, in ticket order, are owned by no wave: whoever draws
+    // such a unit's ticket RESOLVEs it into the block-shared records trec and
+    // publishes lds_tready[unit] (fence, then flag, like a segment's flag), and
+    // a wave without an owned unit left pulls the tail's STEPS one by one from
+    // a third counter (step ticket t: unit t / GS, step t % GS), loads the
+    // step's parent rows PD steps ahead as everywhere, breeds with the same
+    // arithmetic and takes the per-step epilogue.  The RNG is keyed per child,
+    // best is a max, the histogram is atomic adds and the statistics are
+    // exact integer sums (the unit loop's bound), so who breeds a step does
+    // not show in any output.
+    // Progress.  A wave waits for lds_tready[u] only after it has seen u's
+    // unit ticket drawn (lds_next counts past it), drawing tickets itself
+    // until then and resolving each tail unit it draws BEFORE it waits for
+    // anything (TSERVE).  The flag of u is thus always owed by a wave that has
+    // drawn u's ticket and that, between the draw and the flag, runs nothing
+    // but RESOLVE, whose own waits (lds_pro, the segment flags) are on waves in
+    // their tournament phase, which wait on nothing.  No wave waits on a tail
+    // flag before its own pending unit is published, so there is no cycle.
+    // No wave resolves the tail alone either: the waves of the unit loop draw
+    // one ticket per unit they enter, which hands the first tail units to up
+    // to 16 different waves, and a wave in the tail loop draws at most one
+    // more ticket per step it pulls while any is left.  Every spin sleeps.
+    // The round's last barrier releases trec, lds_tstep and the flags.
+#define PGA_TP_TPULL(TQ) TQ = tp_ticket(&lds_tstep, lane);
+    // resolve the pending tail unit; draw until NEEDT unit tickets are drawn
+    // (0: none needed), and one more if EAGER and any is left
+#define PGA_TP_TSERVE(NEEDT, EAGER)                                                                         \
+  {                                                                                                         \
+    bool eg_ = (EAGER);                                                                                     \
+    for (;;) {                                                                                              \
+      if (tpend != kNoUnit) {                                                                               \
+        const uint32_t ts_ = rbeg + (nown + tpend) * 64u;                                                   \
+        const uint32_t te_ = ts_ + 64u < rend ? ts_ + 64u : rend;                                           \
+        PGA_TP_RESOLVE_TO(ts_, te_, trec[tpend])                                                            \
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");                                              \
+        tp_flag_set(&lds_tready[tpend]);                                                                    \
+        tpend = kNoUnit;                                                                                    \
+      }                                                                                                     \
+      const uint32_t d_ = __builtin_amdgcn_readfirstlane(__hip_atomic_load(                                 \
+                              &lds_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) >> 6;             \
+      if (d_ >= (NEEDT) && !(eg_ && d_ < nu)) break;                                                        \
+      eg_ = false;                                                                                          \
+      const uint32_t tk_ = tp_ticket(&lds_next, lane);                                                      \
+      if (tk_ >= nown && tk_ < nu) tpend = tk_ - nown;                                                      \
+    }                                                                                                       \
+  }
+    // unit tickets that must be drawn before step ticket TQ can be waited for
+#define PGA_TP_TNEED(TQ) ((TQ) < ntst ? nown + (TQ) / (uint32_t)GS + 1u : 0u)
+    // wait for the records of step ticket TQ's unit (wave-uniform spin)
+#define PGA_TP_TWAIT(TQ)                                                                                    \
+  if ((TQ) < ntst) {                                                                                        \
+    PGA_TP_TSPIN0                                                                                           \
+    while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&lds_tready[(TQ) / (uint32_t)GS], __ATOMIC_RELAXED, \
+                                                             __HIP_MEMORY_SCOPE_WORKGROUP)) == 0u)          \
+      __builtin_amdgcn_s_sleep(1);                                                                          \
+    PGA_TP_TSPIN1                                                                                           \
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");                                                  \
+  }
+#ifdef PGA_TP_TIMING
+#define PGA_TP_TSPIN0 const unsigned long long tsp0_ = clock64();
+#define PGA_TP_TSPIN1 clk_tflag += clock64() - tsp0_;
+#else
+#define PGA_TP_TSPIN0
+#define PGA_TP_TSPIN1
+#endif
+
     uint32_t ns, ne = 0;  // the wave's next unit (prefetched ticket)
     PGA_TP_NEXT(ns, ne)
-    if (ns != kNoUnit) {
+    const bool own = ns != kNoUnit;  // the wave drew an owned unit
+    const bool tailm = TAILF && U == 64u && ntst > 0u;  // the round has tail steps
+    if (own || tailm) {
       // breed cursor: ring slot, step and its unit [bs, be).  Every unit
       // takes its full nst = U / NG steps, a partial one (only ever at S)
       // too: its children past S write the padding rows, and a unit never
       // holds fewer steps than the PD the load cursor runs ahead
       uint32_t slot = 0, i = 0, bs = ns, be = ne;
-      PGA_TP_NEXT(ns, ne)
-      PGA_TP_RESOLVE(bs, be, 0u)
+      if (own) {
+        PGA_TP_NEXT(ns, ne)
+        PGA_TP_RESOLVE(bs, be, 0u)
+      }
       // load cursor of the rotating loop; lpend: at the end of its unit with
       // unit ns next; lmore = false: past the wave's last step
       uint32_t lslot = 0, li = 0, lbs = bs, lbe = be;
@@ -729,11 +846,12 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
       // BREED step I of the breed cursor's unit from the parent rows (XA, XB):
       // child c = bs + I * NG + g, its row v stored, its score sc (uniform
       // over the group's lanes; JIT: evaluated later).  Children past S, at
-      // the population's end only, write the padding rows.  Shared by the two
-      // loop forms; c, v and sc stay in the enclosing scope.
-#define PGA_TP_BREED(XA, XB, I)                                                                             \
+      // the population's end only, write the padding rows.  R: the unit's
+      // records (the wave's ring slot, or a tail unit's shared ones).  Shared
+      // by the loop forms; c, v and sc stay in the enclosing scope.
+#define PGA_TP_BREED(XA, XB, I, R)                                                                          \
     const uint32_t c = bs + (I) * NG + g;                                                                   \
-    const uint4 r0 = rec[slot][(I) * NG + g][0];                                                            \
+    const uint4 r0 = (R)[(I) * NG + g][0];                                                                  \
     const uint32_t meta = r0.w;                                                                             \
     const uint4 m = range ? range_keep_a(q, r0.z & 0xFFFFu, r0.z >> 16) : u4(draw<true>(a.key, ST_XO, c, q)); \
     uint4 v = mix4(XA, XB, m);                                                                              \
@@ -745,7 +863,7 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
     } else {                                                                                                \
       const uint32_t K = meta & 0xFFu;                                                                      \
       if (K > 0u) {                                                                                         \
-        const uint4 r1 = rec[slot][(I) * NG + g][1];                                                        \
+        const uint4 r1 = (R)[(I) * NG + g][1];                                                              \
         const uint32_t kk = K < kRecPos ? K : kRecPos;                                                      \
         /* the first 4 unrolled (a loop here costs ~20 VGPRs of the whole kernel) */                       \
         _Pragma("unroll") for (uint32_t k = 0; k < 4; ++k) {                                               \
@@ -794,7 +912,7 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
 #define PGA_TP_STEP(XA, XB, YA, YB)                                                                         \
   {                                                                                                         \
     PGA_TP_LOAD(YA, YB)                                                                                     \
-    PGA_TP_BREED(XA, XB, i)                                                                                 \
+    PGA_TP_BREED(XA, XB, i, rec[slot])                                                                      \
     if constexpr (JIT) {                                                                                    \
       lds_stage[(i % kJitStageSteps) * 64u + lane] = v;                                                     \
       if (i % kJitStageSteps == kJitStageSteps - 1u || i + 1u == nst) PGA_TP_JIT_EVAL                       \
@@ -834,15 +952,19 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
   }
 #ifdef PGA_TP_TIMING
 #define PGA_TP_COUNT n_bred += be - bs;
+#define PGA_TP_TCOUNT n_bred += NG, n_tail += 1;
 #else
 #define PGA_TP_COUNT
+#define PGA_TP_TCOUNT
 #endif
 
       // one step I of the UNIT loop (full units: GS steps, the load cursor a
       // static PD steps ahead; the exact-key objectives only, UNITF): the loads
       // of step I + PD into (YA, YB) -- from step GS - PD on in the wave's next
       // unit, RESOLVEd into the other ring slot there, once; a wave without
-      // one re-reads its own step's rows -- then breed step I from (XA, XB)
+      // one loads its first PD TAIL steps' rows there instead, so that it goes
+      // over to the tail loop with its loads in flight, or, with no tail step
+      // left either, re-reads its own step's rows -- then breed step I from (XA, XB)
       // and move the group's score to lane I * NG + group (one ds_bpermute and
       // a select); nothing but the row is stored per step.
       // Before the arithmetic the step waits until the rows of step I + 1
@@ -861,16 +983,40 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
         nbe = ne;                                                                                           \
         PGA_TP_NEXT(ns, ne)                                                                                 \
       }                                                                                                     \
+      /* TAIL, at most twice per wave and round (unlikely: laid out outside the unit's straight line): */  \
+      /* a tail unit the ticket above drew, or, without a next unit, the hand-over: the first PD tail  */  \
+      /* steps take the load cursor's place                                                            */  \
+      if (__builtin_expect(tailm && (!hn || tpend != kNoUnit), 0)) {                                        \
+        if (!hn) {                                                                                          \
+          PGA_TP_TPULL(tq0)                                                                                 \
+          PGA_TP_TPULL(tq1)                                                                                 \
+        }                                                                                                   \
+        const uint32_t tqm_ = tq1 < ntst ? tq1 : tq0;                                                       \
+        PGA_TP_TSERVE(hn ? 0u : PGA_TP_TNEED(tqm_), false)                                                  \
+        if (!hn) {                                                                                          \
+          PGA_TP_TWAIT(tq0)                                                                                 \
+          PGA_TP_TWAIT(tq1)                                                                                 \
+          /* where the two steps' records start in LDS (uniform), so that the loads below take a select */ \
+          /* and the unit stays one straight line                                                        */ \
+          uo0 = tq0 < ntst ? toff + tq0 / (uint32_t)GS * kTpTailUnitBytes + tq0 % (uint32_t)GS * (NG * 32u) : kNoUnit; \
+          uo1 = tq1 < ntst ? toff + tq1 / (uint32_t)GS * kTpTailUnitBytes + tq1 % (uint32_t)GS * (NG * 32u) : kNoUnit; \
+        }                                                                                                   \
+      }                                                                                                     \
     }                                                                                                       \
     const bool un_ = ul_ >= (uint32_t)GS;                                                                   \
-    const uint4 ur_ = rec[un_ && hn ? slot ^ 1u : slot][(un_ ? (hn ? ul_ - GS : (I)) : ul_) * NG + g][0];   \
+    const uint4* up_ = &rec[un_ && hn ? slot ^ 1u : slot][(un_ ? (hn ? ul_ - GS : (I)) : ul_) * NG + g][0]; \
+    if (un_) { /* (compile time) the hand-over: a tail step's records */                                    \
+      const uint32_t uo_ = ul_ == (uint32_t)GS ? uo0 : uo1;                                                 \
+      up_ = uo_ != kNoUnit ? (const uint4*)(pga_dyn_lds + (uo_ + g * 32u)) : up_;                           \
+    }                                                                                                       \
+    const uint4 ur_ = *up_;                                                                                 \
     YA = ROW(cur, ur_.x, qq);                                                                               \
     YB = ROW(cur, ur_.y, qq);                                                                               \
     {                                                                                                       \
       const uint32_t w_ = NA.x | NB.x;                                                                      \
       asm volatile("" ::"v"(w_));                                                                           \
     }                                                                                                       \
-    PGA_TP_BREED(XA, XB, I)                                                                                 \
+    PGA_TP_BREED(XA, XB, I, rec[slot])                                                                      \
     const float t_ = __shfl(sc, (int)usrc, 64);                                                             \
     usc = lane / NG == (I) ? t_ : usc;                                                                      \
   }
@@ -886,55 +1032,128 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
         // has left the current one
         bool hn = false;
         uint32_t nbs = 0, nbe = 0;
-        {
-          const uint4 r = rec[0][g][0];
-          A0 = ROW(cur, r.x, qq);
-          B0 = ROW(cur, r.y, qq);
-        }
-        {
-          const uint4 r = rec[0][NG + g][0];
-          A1 = ROW(cur, r.x, qq);
-          B1 = ROW(cur, r.y, qq);
-        }
-        for (;;) {
-#pragma unroll
-          for (uint32_t u = 0; u < (uint32_t)GS; u += 4u) {  // one rotation of the four register sets
-            PGA_TP_USTEP(u, A0, B0, A2, B2, A1, B1)
-            PGA_TP_USTEP(u + 1u, A1, B1, A3, B3, A2, B2)
-            PGA_TP_USTEP(u + 2u, A2, B2, A0, B0, A3, B3)
-            PGA_TP_USTEP(u + 3u, A3, B3, A1, B1, A0, B0)
+        // TAIL: the step tickets whose rows the register sets hold (>= ntst: none)
+        uint32_t tq0 = kNoUnit, tq1 = kNoUnit, tq2 = kNoUnit;
+        uint32_t uo0 = kNoUnit, uo1 = kNoUnit;  // the hand-over: LDS offsets of the records of tq0, tq1
+        if (tailm) {
+          // the tail unit a first ticket drew; a wave that owns no unit at all
+          // starts with the tail's next PD steps.  (Its two pairs of row loads
+          // below are the one place where a vector memory operation of this
+          // kernel sits under a condition: once per wave and round, before the
+          // loop and with nothing in flight that a merged wait could drain.)
+          if (!own) {
+            PGA_TP_TPULL(tq0)
+            PGA_TP_TPULL(tq1)
           }
-          // The unit's epilogue, once per child: lane j holds the score of
-          // child bs + j.  Statistics: every lane now adds one child per unit
-          // where lane q == 0 of a group added GS.  The scores are
-          // non-negative integers (exact keys, <= 65535), so every per-lane,
-          // per-wave and per-block partial sum is bounded by the block's
-          // total; while that is below 2^24 all of them are exact in f32 and
-          // the block's {min, sum} equals the rotating loop's bit for bit.
-          // Above it (a block share x mean score >= 2^24: from S ~ 8 M at
-          // L = 1024 on 256 CUs) the rotating loop's sum already depends on
-          // which wave pulled which unit, i.e. it differs from run to run;
-          // the launcher's users that need exact sums check the same bound
-          // (roulette_fused_launch).
+          const uint32_t tqm_ = tq1 < ntst ? tq1 : tq0;
+          PGA_TP_TSERVE(PGA_TP_TNEED(tqm_), false)
+          PGA_TP_TWAIT(tq0)
+          PGA_TP_TWAIT(tq1)
+          if (tq0 < ntst) {
+            const uint32_t t1_ = tq1 < ntst ? tq1 : tq0;
+            const uint4 r = trec[tq0 / (uint32_t)GS][(tq0 % (uint32_t)GS) * NG + g][0];
+            A0 = ROW(cur, r.x, qq);
+            B0 = ROW(cur, r.y, qq);
+            const uint4 r1 = trec[t1_ / (uint32_t)GS][(t1_ % (uint32_t)GS) * NG + g][0];
+            A1 = ROW(cur, r1.x, qq);
+            B1 = ROW(cur, r1.y, qq);
+          }
+        }
+        if (own) {
           {
-            const uint32_t c = bs + lane;
-            ELEM(float, a.score_next, c) = usc;
-            ELEM(uint16_t, a.key_next, c) = (uint16_t)usc;
-            if (hist && c < S) {
-              const uint32_t kb = (uint16_t)usc;
-              __hip_atomic_fetch_add(&lds_hist[kb < hmax ? kb : hmax], 1u, __ATOMIC_RELAXED,
-                                     __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-            const unsigned long long pk = c < S ? pack_best(usc, c) : 0ull;
-            my_best = pk > my_best ? pk : my_best;
-            st.add_if(c < S, usc);
+            const uint4 r = rec[0][g][0];
+            A0 = ROW(cur, r.x, qq);
+            B0 = ROW(cur, r.y, qq);
           }
-          PGA_TP_COUNT
-          if (!hn) break;  // the load cursor never left this unit: it was the wave's last
-          slot ^= 1u;
-          bs = nbs;
-          be = nbe;
+          {
+            const uint4 r = rec[0][NG + g][0];
+            A1 = ROW(cur, r.x, qq);
+            B1 = ROW(cur, r.y, qq);
+          }
+          for (;;) {
+#pragma unroll
+            for (uint32_t u = 0; u < (uint32_t)GS; u += 4u) {  // one rotation of the four register sets
+              PGA_TP_USTEP(u, A0, B0, A2, B2, A1, B1)
+              PGA_TP_USTEP(u + 1u, A1, B1, A3, B3, A2, B2)
+              PGA_TP_USTEP(u + 2u, A2, B2, A0, B0, A3, B3)
+              PGA_TP_USTEP(u + 3u, A3, B3, A1, B1, A0, B0)
+            }
+            // The unit's epilogue, once per child: lane j holds the score of
+            // child bs + j.  Statistics: every lane now adds one child per unit
+            // where lane q == 0 of a group added GS.  The scores are
+            // non-negative integers (exact keys, <= 65535), so every per-lane,
+            // per-wave and per-block partial sum is bounded by the block's
+            // total; while that is below 2^24 all of them are exact in f32 and
+            // the block's {min, sum} equals the rotating loop's bit for bit.
+            // Above it (a block share x mean score >= 2^24: from S ~ 8 M at
+            // L = 1024 on 256 CUs) the rotating loop's sum already depends on
+            // which wave pulled which unit, i.e. it differs from run to run;
+            // the launcher's users that need exact sums check the same bound
+            // (roulette_fused_launch).
+            {
+              const uint32_t c = bs + lane;
+              ELEM(float, a.score_next, c) = usc;
+              ELEM(uint16_t, a.key_next, c) = (uint16_t)usc;
+              if (hist && c < S) {
+                const uint32_t kb = (uint16_t)usc;
+                __hip_atomic_fetch_add(&lds_hist[kb < hmax ? kb : hmax], 1u, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_WORKGROUP);
+              }
+              const unsigned long long pk = c < S ? pack_best(usc, c) : 0ull;
+              my_best = pk > my_best ? pk : my_best;
+              st.add_if(c < S, usc);
+            }
+            PGA_TP_COUNT
+            if (!hn) break;  // the load cursor never left this unit: it was the wave's last
+            slot ^= 1u;
+            bs = nbs;
+            be = nbe;
+          }
+        }  // if (own)
+        // one step of the TAIL loop: pull the step PD ahead (ticket TY) and load
+        // its rows into (YA, YB) -- none left: re-read the breed cursor's --,
+        // wait for the next step's rows (NA, NB) as the unit loop does, breed
+        // the step of ticket TX from (XA, XB) with the per-step epilogue
+#define PGA_TP_TSTEP(XA, XB, YA, YB, NA, NB, TX, TY)                                                        \
+  {                                                                                                         \
+    PGA_TP_TPULL(TY)                                                                                        \
+    PGA_TP_TSERVE(PGA_TP_TNEED(TY), TY < ntst)                                                              \
+    PGA_TP_TWAIT(TY)                                                                                        \
+    {                                                                                                       \
+      const uint32_t tl_ = TY < ntst ? TY : TX;                                                             \
+      const uint4 tr_ = trec[tl_ / (uint32_t)GS][(tl_ % (uint32_t)GS) * NG + g][0];                         \
+      YA = ROW(cur, tr_.x, qq);                                                                             \
+      YB = ROW(cur, tr_.y, qq);                                                                             \
+    }                                                                                                       \
+    {                                                                                                       \
+      const uint32_t w_ = NA.x | NB.x;                                                                      \
+      asm volatile("" ::"v"(w_));                                                                           \
+    }                                                                                                       \
+    {                                                                                                       \
+      const uint32_t tu_ = TX / (uint32_t)GS, ti_ = TX % (uint32_t)GS;                                      \
+      const uint32_t bs = rbeg + (nown + tu_) * 64u;                                                        \
+      PGA_TP_BREED(XA, XB, ti_, trec[tu_])                                                                  \
+      PGA_TP_STEP_SCORE                                                                                     \
+    }                                                                                                       \
+    PGA_TP_TCOUNT                                                                                           \
+  }
+        if (tailm) {
+#ifdef PGA_TP_TIMING
+          const unsigned long long clkT = clock64();
+#endif
+          for (;;) {
+            if (tq0 >= ntst) break;
+            PGA_TP_TSTEP(A0, B0, A2, B2, A1, B1, tq0, tq2)
+            if (tq1 >= ntst) break;
+            PGA_TP_TSTEP(A1, B1, A0, B0, A2, B2, tq1, tq0)
+            if (tq2 >= ntst) break;
+            PGA_TP_TSTEP(A2, B2, A1, B1, A0, B0, tq2, tq1)
+          }
+#ifdef PGA_TP_TIMING
+          clk_tail += clock64() - clkT;
+#endif
         }
+#undef PGA_TP_TSTEP
       } else if constexpr (PD == 1) {
         PGA_TP_LOAD(A0, B0)
         for (;;) {
@@ -977,8 +1196,16 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
 #undef PGA_TP_NEXT
 #undef PGA_TP_JIT_EVAL
 #undef PGA_TP_COUNT
+#undef PGA_TP_TCOUNT
     }
+#undef PGA_TP_TPULL
+#undef PGA_TP_TSERVE
+#undef PGA_TP_TNEED
+#undef PGA_TP_TWAIT
+#undef PGA_TP_TSPIN0
+#undef PGA_TP_TSPIN1
 #undef PGA_TP_RESOLVE
+#undef PGA_TP_RESOLVE_TO
 #undef PGA_TP_SPIN0
 #undef PGA_TP_SPIN1
 #ifdef PGA_TP_TIMING
@@ -992,6 +1219,10 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
 #endif
     if (threadIdx.x == 0) lds_next = lds_tnext = 0;
     if (threadIdx.x < kTpMaxSegs) lds_ready[threadIdx.x] = 0;
+    if constexpr (TAILF) {
+      if (threadIdx.x == 0) lds_tstep = 0;
+      if (threadIdx.x < kTpMaxTail) lds_tready[threadIdx.x] = 0;
+    }
   }
 #undef ROW
 #undef ELEM
@@ -1009,10 +1240,18 @@ __device__ __forceinline__ void binary_gen_tp_body(GenArgs a, unsigned long long
     pga_tp_clk[wv][8] = clk_sync0;   // ... at the first round's first barrier
     pga_tp_clk[wv][9] = clk_sync1;   // ... at the rounds' last barriers
     pga_tp_clk[wv][10] = clk_syncn;  // ... at the later rounds' first barriers
+    pga_tp_clk[wv][11] = clk_tail;   // cycles in the tail loop
+    pga_tp_clk[wv][12] = n_tail;     // tail steps the wave bred
+    pga_tp_clk[wv][13] = clk_tflag;  // cycles it waited for tail units' flags
   }
 #endif
+  // (the unit loop's kernels: an opaque thread id, so that this loop's bounds
+  // are worked out here and not shared with the zeroing loop at the kernel's
+  // start, in registers across everything between)
+  uint32_t ftid = threadIdx.x;
+  if constexpr (TAILF) asm volatile("" : "+v"(ftid));
   if (hist)  // every wave passed the last round's barrier: the block's counts are complete
-    for (uint32_t i = threadIdx.x; i < a.hist_bins; i += blockDim.x) {
+    for (uint32_t i = ftid; i < a.hist_bins; i += blockDim.x) {
       const uint32_t v = lds_hist[i];
       if (a.key_hist && v) __hip_atomic_fetch_add(&a.key_hist[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (a.rank_counts) a.rank_counts[i * gridDim.x + blockIdx.x] = v;  // this block's sort tile

@@ -365,6 +365,11 @@ struct GenArgs {
   // share skew of binary_gen_tp (tp.hpp tp_share): units each odd block of a
   // pair hands to its even neighbour (0: equal shares)
   uint32_t tp_skew;
+  // tail units of binary_gen_tp's unit loop (tp.hpp kTpMaxTail): the last
+  // tp_tail units of a block's round are bred step by step by whichever wave
+  // is free; the launcher adds their shared records to the launch's dynamic
+  // LDS (0: every unit is bred by the wave that drew it)
+  uint32_t tp_tail;
   // encoding-specific derived objective table, nullptr when unused
   // (PERMUTATION, perm.hip: the integer distance matrix as u16, kind 1 = a
   // symmetric matrix's strict lower triangle then its diagonal, 2 = the

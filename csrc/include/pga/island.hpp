@@ -217,6 +217,9 @@ class Island {
   // BINARY knapsack: int8 digits per value of the matrix-core evaluation
   // (0: the instance is not integer-exact and runs the scalar evaluation)
   uint32_t knapsack_digits() const { return knap_dig_; }
+  // tail units of the last generation launch (binary_gen_tp's TAIL steps,
+  // ops.hpp TpPartition::tail): 0 when the launch had none
+  uint32_t tp_tail() const { return tp_tail_; }
 
   // checkpoint: header + current rows + scores
   void save(const std::string& path);
@@ -282,6 +285,7 @@ class Island {
   // stats_part_[p]: the block partition of the binary_gen_tp launch whose
   // partials stats_parts_[p] holds (grid 0: another kernel wrote them)
   TpPartition stats_part_[2] = {{0, 0, 0}, {0, 0, 0}};
+  uint32_t tp_tail_ = 0;
   void set_stats_ok(int p, bool ok) {
     stats_ok_[p] = ok;
     stats_part_[p] = TpPartition{0, 0, 0};

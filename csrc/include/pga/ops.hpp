@@ -57,6 +57,12 @@ uint32_t tp_dyn_lds_bytes(uint32_t nw, uint32_t pseg = 7);
 uint32_t tp_jit_stage_bytes(uint32_t nw);
 // share skew for this geometry (tp.hpp tp_share; PGA_TP_SKEW units, default 2)
 uint32_t tp_skew_units(const TpGeom& t, uint64_t S);
+// tail units of binary_gen_tp's unit loop for this geometry (GenArgs::tp_tail;
+// PGA_TP_TAIL units, read once), lowered to what fits: gs = the group size,
+// used = the launch's dynamic LDS without the tail's records (they follow it,
+// tp.hpp tp_tail_off), avail = what allow_dynamic_lds returned for the kernel
+constexpr uint32_t kTpTailDefault = 16;
+uint32_t tp_tail_units(const TpGeom& t, uint32_t gs, uint32_t used, size_t avail);
 int device_cu_count();
 // raise a kernel's dynamic-LDS limit to what its static LDS leaves of the
 // CU's 160 KiB on the current device (once per kernel and device; cheap to
@@ -82,8 +88,11 @@ bool& binary_rank_counts_written();
 // (grid 0: the launch took another kernel): block j wrote children
 // tp_share(S, unit, j, skew) and stored their {min, sum} partials at
 // stats_parts[2 j] (no pair pool)
+// tail: the tail units the launch asked for (GenArgs::tp_tail after the LDS
+// clamp; 0: a kernel without tail steps, or none fit)
 struct TpPartition {
   uint32_t grid, unit, skew;
+  uint32_t tail = 0;
 };
 TpPartition& binary_tp_partition();
 // whether a MODE_GEN launch of these arguments takes the hot two-phase kernel

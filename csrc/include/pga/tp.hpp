@@ -204,6 +204,13 @@ __host__ __device__ constexpr uint32_t tp_dyn_lds(uint32_t nw, uint32_t pseg = 7
   return nw * 4096u + tp_par_cap(nw, pseg) * 8u;
 }
 static_assert(tp_par_cap(4) % (kSegBatches * 64) == 0, "rounds hold whole segments");
+// TAIL units of binary_gen_tp's unit loop (binary_dev.hpp): the last units of a
+// 16-wave block's round are bred step by step by whichever wave is free, from
+// block-shared records: 64 x 32 B per tail unit, 16-byte aligned behind
+// everything else in dynamic LDS (records, parents, histogram bins)
+constexpr uint32_t kTpMaxTail = 32;
+constexpr uint32_t kTpTailUnitBytes = 64u * 32u;
+__host__ __device__ constexpr uint32_t tp_tail_off(uint32_t used) { return (used + 15u) & ~15u; }
 // fused BINARY JIT kernels (binary_dev.hpp): steps of children staged in LDS
 // per objective pass, 1 KB per wave per step after the parents (16 waves:
 // 120 + 32 KB of dynamic LDS); tp_jit_stage_lds is what the launch adds

@@ -23,19 +23,28 @@ uint32_t batch_go(GenBatch& b, uint32_t n, uint64_t S, bool full, bool dense, hi
                                 : (const void*)binary_gen_tp_batch<GS, OBJ, false, false>);
   // the device split between the islands (tp_geometry)
   const TpGeom t = tp_geometry(S, n, k, 64 / GS);
+  // the unit loop's tail units (binary_dev.hpp, TAIL) after the parents; an
+  // island whose kernel would use LDS histogram bins there gets none
+  bool bins = false;
+  for (uint32_t i = 0; i < n; ++i) bins = bins || b.a[i].rank_counts != nullptr;
+  constexpr bool key_obj = OBJ == OBJ_ONEMAX || OBJ == OBJ_LEADING_ONES || OBJ == OBJ_TRAP;  // (go_tp's gate)
+  const uint32_t tail = !key_obj || bins ? 0u : tp_tail_units(t, GS, t.lds, allow_dynamic_lds(k));
+  const uint32_t lds = tail > 0 ? dev::tp_tail_off(t.lds) + tail * dev::kTpTailUnitBytes : t.lds;
   for (uint32_t i = 0; i < n; ++i) {
     b.a[i].tp_unit = t.unit;
+    b.a[i].tp_tail = tail;
     b.a[i].key_hist = nullptr;  // no fused histogram in the batched launch (no LDS for it)
   }
   const dim3 grid(t.grid, n);
   if (full) {
-    if (dense) hipLaunchKernelGGL((binary_gen_tp_batch<GS, OBJ, true, true>), grid, t.block, t.lds, s, b);
-    else hipLaunchKernelGGL((binary_gen_tp_batch<GS, OBJ, true, false>), grid, t.block, t.lds, s, b);
+    if (dense) hipLaunchKernelGGL((binary_gen_tp_batch<GS, OBJ, true, true>), grid, t.block, lds, s, b);
+    else hipLaunchKernelGGL((binary_gen_tp_batch<GS, OBJ, true, false>), grid, t.block, lds, s, b);
   } else {
-    if (dense) hipLaunchKernelGGL((binary_gen_tp_batch<GS, OBJ, false, true>), grid, t.block, t.lds, s, b);
-    else hipLaunchKernelGGL((binary_gen_tp_batch<GS, OBJ, false, false>), grid, t.block, t.lds, s, b);
+    if (dense) hipLaunchKernelGGL((binary_gen_tp_batch<GS, OBJ, false, true>), grid, t.block, lds, s, b);
+    else hipLaunchKernelGGL((binary_gen_tp_batch<GS, OBJ, false, false>), grid, t.block, lds, s, b);
   }
   PGA_HIP_CHECK(hipGetLastError());
+  binary_tp_partition() = TpPartition{t.grid, t.unit, 0, tail};  // (every island of the batch)
   return t.grid;
 }
 

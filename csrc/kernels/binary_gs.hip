@@ -49,10 +49,15 @@ uint32_t go_tp(K kernel, const GenArgs& a0, unsigned long long* parts, hipStream
                   (a.S + t.grid - 1) / t.grid == kRankTile && (uint64_t)t.grid == (a.S + kRankTile - 1) / kRankTile;
   if (rk) a.tp_skew = 0;
   else a.rank_counts = nullptr;
-  hipLaunchKernelGGL(kernel, t.grid, t.block, t.lds + (hist || rk ? 4u * a.hist_bins : 0u), s, a, parts);
+  // the unit loop's tail units (binary_dev.hpp, TAIL): their shared records
+  // follow everything else, as many as the kernel's dynamic LDS limit admits
+  uint32_t lds = t.lds + (hist || rk ? 4u * a.hist_bins : 0u);
+  a.tp_tail = key_obj ? tp_tail_units(t, group_size(a.chunks), lds, allow_dynamic_lds((const void*)kernel)) : 0u;
+  if (a.tp_tail > 0) lds = tp_tail_off(lds) + a.tp_tail * kTpTailUnitBytes;
+  hipLaunchKernelGGL(kernel, t.grid, t.block, lds, s, a, parts);
   binary_hist_written() = hist;
   binary_rank_counts_written() = rk;
-  binary_tp_partition() = TpPartition{t.grid, tp_unit(a, 64u / group_size(a.chunks)), a.tp_skew};
+  binary_tp_partition() = TpPartition{t.grid, tp_unit(a, 64u / group_size(a.chunks)), a.tp_skew, a.tp_tail};
   return t.grid;
 }
 
@@ -129,7 +134,7 @@ uint32_t binary_launch_group<PGA_BIN_GS>(int mode, const GenArgs& a, unsigned lo
 extern "C" void pga_tp_timing_dump(uint32_t nwaves) {
   static unsigned long long h[kMaxGrid * 4][kTpClkWords];  // per wave: blockIdx.x * waves + wave
   PGA_HIP_CHECK(hipMemcpyFromSymbol(h, HIP_SYMBOL(pga_tp_clk), sizeof(h)));
-  double t = 0, b = 0, tot = 0, n = 0, mx = 0, s0 = 0, sn = 0, s1 = 0;
+  double t = 0, b = 0, tot = 0, n = 0, mx = 0, s0 = 0, sn = 0, s1 = 0, tl = 0, tn = 0, tf = 0;
   unsigned long long rt_min = ~0ull, rt_max = 0, st_max = 0;
   uint32_t nw = 0;
   for (uint32_t i = 0; i < nwaves && i < kMaxGrid * 4; ++i) {
@@ -140,6 +145,9 @@ extern "C" void pga_tp_timing_dump(uint32_t nwaves) {
     s0 += (double)h[i][8];
     s1 += (double)h[i][9];
     sn += (double)h[i][10];
+    tl += (double)h[i][11];
+    tn += (double)h[i][12];
+    tf += (double)h[i][13];
     mx = std::max(mx, (double)h[i][2]);
     n += 1;
     rt_min = std::min(rt_min, h[i][4]);
@@ -149,10 +157,11 @@ extern "C" void pga_tp_timing_dump(uint32_t nwaves) {
   }
   std::printf("{\"tp_timing\": {\"waves\": %.0f, \"tourn_cycles\": %.0f, \"breed_cycles\": %.0f, "
               "\"first_barrier_cycles\": %.0f, \"later_first_barrier_cycles\": %.0f, "
-              "\"last_barrier_cycles\": %.0f, "
+              "\"last_barrier_cycles\": %.0f, \"tail_cycles\": %.0f, \"tail_steps\": %.2f, "
+              "\"tail_flag_wait_cycles\": %.0f, "
               "\"wave_cycles\": %.0f, \"max_wave_cycles\": %.0f, \"tourn_frac\": %.3f, "
               "\"span_us\": %.2f, \"last_start_us\": %.2f}}\n",
-              n, t / n, b / n, s0 / n, sn / n, s1 / n, tot / n, mx, t / (t + b), (rt_max - rt_min) / 100.0,
+              n, t / n, b / n, s0 / n, sn / n, s1 / n, tl / n, tn / n, tf / n, tot / n, mx, t / (t + b), (rt_max - rt_min) / 100.0,
               (st_max - rt_min) / 100.0);
   // wall-clock end time (us after the first start, 100 MHz clock) per XCD and
   // by block order (older blocks first): is the tail an XCD or an age effect?

@@ -103,6 +103,22 @@ uint32_t tp_skew_units(const TpGeom& t, uint64_t S) {
   return d * 4 < units ? d : 0u;
 }
 
+uint32_t tp_tail_units(const TpGeom& t, uint32_t gs, uint32_t used, size_t avail) {
+  // PGA_TP_TAIL = the last units of a 16-wave block's round that are bred
+  // step by step by whichever wave is free (binary_dev.hpp, TAIL); 0: none
+  static const uint32_t d = [] {
+    const char* e = std::getenv("PGA_TP_TAIL");
+    return e ? (uint32_t)std::strtoul(e, nullptr, 10) : kTpTailDefault;
+  }();
+  // the unit loop's launches at GS 8 only (binary_dev.hpp TAILF): 64-child units of 8 steps on the 16-wave block
+  if (d == 0 || t.block != dev::kTpMaxWaves * 64 || t.unit != 64 || gs != 8) return 0;
+  uint32_t n = d < dev::kTpMaxTail ? d : dev::kTpMaxTail;
+  const size_t off = dev::tp_tail_off(used);
+  if (off >= avail) return 0;
+  const size_t fit = (avail - off) / dev::kTpTailUnitBytes;  // what the CU's LDS leaves: fewer tail units, not a failed launch
+  return n < fit ? n : (uint32_t)fit;
+}
+
 TpGeom tp_geometry_occ(uint64_t S, uint32_t islands, uint32_t occ4, uint32_t ng, uint32_t pseg) {
   if (islands == 0) islands = 1;
   if (ng == 0 || ng > 64) ng = 64;

@@ -199,6 +199,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_property("graph_generations", &Island::graph_generations, &Island::set_graph_generations)
       .def_property_readonly("graph_replays", &Island::graph_replays)
       .def_property_readonly("knapsack_digits", &Island::knapsack_digits)
+      .def_property_readonly("tp_tail", &Island::tp_tail)
       .def_property("migration_policy", &Island::migration_policy, &Island::set_migration_policy)
       .def_property("fused_histogram", &Island::fused_histogram, &Island::set_fused_histogram)
       .def_property_readonly("fused_histogram_ready", &Island::fused_histogram_ready)
