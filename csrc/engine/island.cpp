@@ -34,7 +34,41 @@ uint32_t prob_thresh(float p) {
   double v = std::floor((double)p * 4294967296.0);
   return v >= 4294967295.0 ? 0xFFFFFFFFu : (v <= 0 ? 0u : (uint32_t)v);
 }
+// A/B knobs: NAME=0 turns a path off (each read once, where it is used)
+bool env_off(const char* name) {
+  const char* e = std::getenv(name);
+  return e && e[0] == '0';
+}
+bool roul_fused_off() {  // PGA_ROUL_FUSED=0: the three-launch roulette prefix
+  static const bool off = env_off("PGA_ROUL_FUSED");
+  return off;
+}
+const char kJitNotTwoOpt[] = "2-opt local search needs a built-in TSP objective, not a JIT objective";
+const char kJitNotOneFlip[] = "one-flip local search needs the built-in QUBO objective, not a JIT objective";
 }  // namespace
+
+Buffer::Buffer(size_t n, bool device) : bytes(n), device_(device) {
+  if (n == 0) return;
+  if (device) {
+    PGA_HIP_CHECK(hipMalloc(&ptr, n));
+  } else {
+    ptr = std::aligned_alloc(64, (n + 63) & ~(size_t)63);
+    if (!ptr) throw std::bad_alloc();
+    std::memset(ptr, 0, n);
+  }
+}
+
+Buffer::~Buffer() {
+  if (!ptr) return;
+  if (device_) (void)hipFree(ptr);
+  else std::free(ptr);
+}
+
+bool Island::reserve(Buffer& b, size_t bytes, bool sync) {
+  if (b.bytes >= bytes) return false;
+  if (sync) synchronize();
+  return b.reserve(bytes, on_gpu());
+}
 
 Island::Island(const Config& cfg, int device) : cfg_(cfg), device_(device) {
   if (cfg_.S == 0) throw std::invalid_argument("population size must be > 0");
@@ -47,14 +81,14 @@ Island::Island(const Config& cfg, int device) : cfg_(cfg), device_(device) {
   const uint64_t Sp = cfg_.S + kRowPad;  // padded (ops.hpp kRowPad)
   const size_t rb = 4ull * row_words_ * Sp;
   for (int i = 0; i < 2; ++i) {
-    rows_[i] = alloc(rb);
-    scores_[i] = alloc(4ull * Sp);
-    best_[i] = alloc(8ull * kMaxGrid);
-    if (on_gpu()) stats_parts_[i] = alloc(8ull * kMaxGrid);
-    keys_[i] = alloc(2ull * Sp);
+    reserve(rows_[i], rb);
+    reserve(scores_[i], 4ull * Sp);
+    reserve(best_[i], 8ull * kMaxGrid);
+    if (on_gpu()) reserve(stats_parts_[i], 8ull * kMaxGrid);
+    reserve(keys_[i], 2ull * Sp);
   }
-  out_best_ = alloc(64);
-  stats_ = alloc(4ull * (4 + 3 * 1024));
+  reserve(out_best_, 64);
+  reserve(stats_, 4ull * (4 + 3 * 1024));
   aux_on_ = std::getenv("PGA_TSP_NO_LDS") == nullptr;  // verification: the f32 L2 matrix path
   if (cfg_.encoding == ENC_BINARY) {
     const uint32_t rem = cfg_.L - 128 * (chunks_ - 1);
@@ -69,50 +103,44 @@ Island::Island(const Config& cfg, int device) : cfg_(cfg), device_(device) {
 }
 
 Island::~Island() {
-  Buffer* all[] = {&rows_[0],   &rows_[1],     &scores_[0],   &scores_[1],  &best_[0],  &best_[1],   &mut_thr_,
-                   &obj_data_[0], &obj_data_[1], &keys_[0], &keys_[1], &elite_idx_, &cumfit_, &cum_ws_, &roul_guide_, &topk_ws_, &stats_,
-                   &out_best_,  &scratch_, &compat_rand_, &ev_parts_, &gen_dev_, &rank_order_, &rank_ws_, &qubo_qt_, &qubo_qn_,
-                   &knap_tab_, &stats_parts_[0], &stats_parts_[1], &hist_, &qk_ws_, &obj_aux_,
-                   &fhist_[0], &fhist_[1], &fhist_[2]};
+  // the graph exec and the capture stream go before the buffers (the members) do
   drop_graph();
   if (cap_stream_) (void)hipStreamDestroy(cap_stream_);
-  for (Buffer* b : all) {
-    try {
-      release(*b);
-    } catch (...) {
-    }
-  }
-}
-
-Buffer Island::alloc(size_t bytes) {
-  Buffer b;
-  b.bytes = bytes;
-  if (bytes == 0) return b;
-  if (on_gpu()) {
-    PGA_HIP_CHECK(hipMalloc(&b.ptr, bytes));
-  } else {
-    b.ptr = std::aligned_alloc(64, (bytes + 63) & ~(size_t)63);
-    if (!b.ptr) throw std::bad_alloc();
-    std::memset(b.ptr, 0, bytes);
-  }
-  return b;
-}
-
-void Island::release(Buffer& b) {
-  if (!b.ptr) return;
-  if (on_gpu()) PGA_HIP_CHECK(hipFree(b.ptr));
-  else std::free(b.ptr);
-  b.ptr = nullptr;
-  b.bytes = 0;
 }
 
 void* Island::scratch(size_t bytes) {
-  if (scratch_.bytes < bytes) {
-    if (on_gpu() && scratch_.ptr) synchronize();
-    release(scratch_);
-    scratch_ = alloc(bytes);
-  }
+  reserve(scratch_, bytes, /*sync=*/scratch_.ptr != nullptr);
   return scratch_.ptr;
+}
+
+// ------------------------------------------------- per-parity record ---
+void Island::scores_written(int p, const Derived& made) {
+  d_[p] = made;
+  if (made.rank_cnt) d_[p ^ 1].rank_cnt = false;  // one workspace
+  if (made.fhist >= 0) {
+    const int z = (made.fhist + 1) % 3;
+    fhist_clean_[made.fhist] = true;  // zeroed (bins and status) by the launch before this one
+    fhist_clean_[z] = true;           // zeroed by this launch
+    if (d_[p ^ 1].fhist == z) d_[p ^ 1].fhist = -1;
+    ++fhist_rot_;
+  }
+}
+
+bool Island::take_rank_counts() {
+  const bool ready = d_[cur_].rank_cnt && !capturing_;
+  d_[0].rank_cnt = d_[1].rank_cnt = false;  // the sort scans them in place
+  return ready;
+}
+
+void Island::drop_key_counts() {
+  d_[0].fhist = d_[1].fhist = -1;
+  d_[0].rank_cnt = d_[1].rank_cnt = false;
+}
+
+void Island::set_n_best(uint32_t n) {
+  d_[cur_].n_best = n;
+  d_[cur_].stats = false;
+  d_[cur_].part = TpPartition{0, 0, 0};
 }
 
 void Island::copy_to_host(void* dst, const void* src, size_t bytes) {
@@ -149,13 +177,13 @@ void Island::rebuild_mut_table() {
                         (cfg_.encoding == ENC_REAL && (cfg_.mutation == MUT_GAUSSIAN || cfg_.mutation == MUT_UNIFORM));
   mut_sparse_ = per_gene && bin_sparse_mutation(cfg_.L, mut_rate_eff_);
   if (mut_sparse_) build_binom_table(mut_rate_eff_, cfg_.L, thr.data());
-  if (!mut_thr_.ptr) mut_thr_ = alloc(4ull * kMutCap);
-  if (on_gpu()) synchronize();
+  reserve(mut_thr_, 4ull * kMutCap);
+  synchronize();
   copy_to_device(mut_thr_.ptr, thr.data(), 4ull * kMutCap);
 }
 
 void Island::set_operators(const Config& c) {
-  invalidate();
+  config_changed();
   if (c.S != cfg_.S || c.L != cfg_.L || c.encoding != cfg_.encoding)
     throw std::invalid_argument("set_operators cannot change S, L or encoding");
   if (c.selection == SEL_TOURNAMENT && (c.tour_k < 1 || c.tour_k > 64))
@@ -178,121 +206,135 @@ void Island::set_operators(const Config& c) {
   cfg_ = c;
   if (!mut_thr_.ptr || old_rate != c.mut_rate || old_mut != c.mutation) rebuild_mut_table();
   fhist_on_ = fhist_user_ || cfg_.n_elite > 1;  // elitism > 1 selects top-k every generation
-  if (cfg_.n_elite > 1 && elite_idx_.bytes < 4ull * cfg_.n_elite) {
-    release(elite_idx_);
-    elite_idx_ = alloc(4ull * cfg_.n_elite);
-  }
-  if (cfg_.selection == SEL_ROULETTE && !cumfit_.ptr) {
-    cumfit_ = alloc(4ull * (cfg_.S + 4));  // + 4: the GEN kernels' 16-byte window loads (tp.hpp)
+  if (cfg_.n_elite > 1) reserve(elite_idx_, 4ull * cfg_.n_elite);
+  if (cfg_.selection == SEL_ROULETTE) {
+    reserve(cumfit_, 4ull * (cfg_.S + 4));  // + 4: the GEN kernels' 16-byte window loads (tp.hpp)
     if (on_gpu()) {
-      cum_ws_ = alloc(4ull * roulette_workspace_floats(cfg_.S));
-      roul_guide_ = alloc(4ull * (cfg_.S + 1));  // guide[0..S]: roulette_bucket's range
+      reserve(cum_ws_, 4ull * roulette_workspace_floats(cfg_.S));
+      reserve(roul_guide_, 4ull * (cfg_.S + 1));  // guide[0..S]: roulette_bucket's range
     }
   }
-  if (cfg_.selection == SEL_RANK && !rank_order_.ptr) {
-    rank_order_ = alloc(4ull * cfg_.S);
-    if (on_gpu()) rank_ws_ = alloc(rank_order_workspace_bytes(cfg_.S));
+  if (cfg_.selection == SEL_RANK) {
+    reserve(rank_order_, 4ull * cfg_.S);
+    if (on_gpu()) reserve(rank_ws_, rank_order_workspace_bytes(cfg_.S));
   }
 }
 
 void Island::set_user_operators(void* xo, void* mut) {
-  invalidate();
+  config_changed();
   if ((xo || mut) && !on_gpu()) throw std::invalid_argument("device function pointers need the GPU backend");
   if ((xo || mut) && cfg_.encoding != ENC_REAL)
     throw std::invalid_argument("user crossover/mutate callbacks need the REAL (float gene) encoding");
   user_xo_fn_ = xo;
   user_mut_fn_ = mut;
-  if ((xo || mut) && !compat_rand_.ptr) compat_rand_ = alloc(4ull * cfg_.S * cfg_.L);
+  if (xo || mut) reserve(compat_rand_, 4ull * cfg_.S * cfg_.L);
 }
 
 void Island::set_objective_data(const float* host, size_t n, int which) {
-  invalidate();
+  config_changed();
   if (which < 0 || which > 1) throw std::invalid_argument("objective data slot must be 0 or 1");
-  if (on_gpu()) synchronize();
-  release(obj_data_[which]);
-  obj_data_[which] = alloc(4ull * (n ? n : 1));
+  synchronize();
+  obj_data_[which] = Buffer();  // a fresh buffer every time, the old one freed first
+  obj_data_[which] = Buffer(4ull * (n ? n : 1), on_gpu());
   if (n) copy_to_device(obj_data_[which].ptr, host, 4ull * n);
   obj_len_[which] = n;
   if (which == 0) obj_host0_.assign(host, host + n);
   ++obj_version_;
 }
 
-void Island::prepare_objective() {
-  if (cfg_.objective == OBJ_KNAPSACK && cfg_.encoding == ENC_BINARY && on_gpu() && knap_version_ != obj_version_) {
-    knap_version_ = obj_version_;
-    knap_dig_ = knap_cols_ = 0;
-    std::vector<uint8_t> tab;
-    if (obj_host0_.size() >= 2ull * cfg_.L &&
-        build_knap_table(obj_host0_.data(), obj_host0_.data() + cfg_.L, cfg_.L, chunks_, tab, knap_dig_, knap_cols_)) {
-      if (knap_tab_.bytes < tab.size()) {
-        release(knap_tab_);
-        knap_tab_ = alloc(tab.size());
-      }
-      copy_to_device(knap_tab_.ptr, tab.data(), tab.size());
-    }
+void Island::prepare_knapsack() {
+  if (cfg_.objective != OBJ_KNAPSACK || cfg_.encoding != ENC_BINARY || !on_gpu() || knap_version_ == obj_version_) return;
+  knap_version_ = obj_version_;
+  knap_dig_ = knap_cols_ = 0;
+  std::vector<uint8_t> tab;
+  if (obj_host0_.size() >= 2ull * cfg_.L &&
+      build_knap_table(obj_host0_.data(), obj_host0_.data() + cfg_.L, cfg_.L, chunks_, tab, knap_dig_, knap_cols_)) {
+    reserve(knap_tab_, tab.size());
+    copy_to_device(knap_tab_.ptr, tab.data(), tab.size());
   }
-  if ((cfg_.objective == OBJ_TSP || cfg_.objective == OBJ_TSP_OPEN) && cfg_.encoding == ENC_PERMUTATION && on_gpu() &&
-      aux_version_ != obj_version_) {
-    // the matrix for the LDS-resident tour evaluation (perm.hip perm_gen_fast
-    // TBL, which reads it): an integer matrix (entries in [0, 65535]) as u16
-    // -- when symmetric the row-major lower triangle with the diagonal, entry
-    // (i, j <= i) at i (i + 1) / 2 + j (kind 1), else the full matrix (kind
-    // 2); any other symmetric matrix as the f32 lower triangle in the same
-    // layout (kind 3); an asymmetric float matrix stays in L2 (kind 0)
-    aux_version_ = obj_version_;
-    aux_kind_ = aux_bytes_ = 0;
-    const uint32_t L = cfg_.L;
-    const float* d = obj_host0_.data();
-    // (only what can fit one CU's LDS: 160 KiB)
-    const size_t tri = (size_t)L * (L + 1) / 2, lds = 160 * 1024;
-    const bool have = obj_host0_.size() >= (size_t)L * L && L >= 2 && 2 * tri <= lds;
-    bool ints = have, sym = have;
-    for (size_t i = 0; ints && i < (size_t)L * L; ++i) ints = d[i] >= 0.f && d[i] <= 65535.f && d[i] == std::floor(d[i]);
-    for (uint32_t i = 0; sym && i < L; ++i)
-      for (uint32_t j = 0; sym && j < i; ++j)
-        sym = std::memcmp(&d[(size_t)i * L + j], &d[(size_t)j * L + i], sizeof(float)) == 0;
-    std::vector<uint8_t> t;
-    auto put = [&t](const auto v) {
-      const size_t o = t.size();
-      t.resize(o + sizeof(v));
-      std::memcpy(t.data() + o, &v, sizeof(v));
-    };
-    if (ints && sym) {
-      for (uint32_t i = 0; i < L; ++i)  // rows of the lower triangle with the diagonal: (i, j <= i) at i (i + 1) / 2 + j
-        for (uint32_t j = 0; j <= i; ++j) put((uint16_t)d[(size_t)i * L + j]);
-      aux_kind_ = 1;
-    } else if (ints && 2ull * L * L <= lds) {
-      for (size_t i = 0; i < (size_t)L * L; ++i) put((uint16_t)d[i]);
-      aux_kind_ = 2;
-    } else if (sym && !ints && 4 * tri <= lds) {
-      for (uint32_t i = 0; i < L; ++i)
-        for (uint32_t j = 0; j <= i; ++j) put(d[(size_t)i * L + j]);
-      aux_kind_ = 3;
-    }
-    if (aux_kind_) {
-      t.resize((t.size() + 15) / 16 * 16, 0);  // whole 16-byte stores
-      if (obj_aux_.bytes < t.size()) {
-        release(obj_aux_);
-        obj_aux_ = alloc(t.size());
-      }
-      copy_to_device(obj_aux_.ptr, t.data(), t.size());
-      aux_bytes_ = (uint32_t)t.size();
-    }
+}
+
+void Island::prepare_tsp_matrix() {
+  if ((cfg_.objective != OBJ_TSP && cfg_.objective != OBJ_TSP_OPEN) || cfg_.encoding != ENC_PERMUTATION || !on_gpu() ||
+      aux_version_ == obj_version_)
+    return;
+  // the matrix for the LDS-resident tour evaluation (perm.hip perm_gen_fast
+  // TBL, which reads it): an integer matrix (entries in [0, 65535]) as u16
+  // -- when symmetric the row-major lower triangle with the diagonal, entry
+  // (i, j <= i) at i (i + 1) / 2 + j (kind 1), else the full matrix (kind
+  // 2); any other symmetric matrix as the f32 lower triangle in the same
+  // layout (kind 3); an asymmetric float matrix stays in L2 (kind 0)
+  aux_version_ = obj_version_;
+  aux_kind_ = aux_bytes_ = 0;
+  const uint32_t L = cfg_.L;
+  const float* d = obj_host0_.data();
+  // (only what can fit one CU's LDS: 160 KiB)
+  const size_t tri = (size_t)L * (L + 1) / 2, lds = 160 * 1024;
+  const bool have = obj_host0_.size() >= (size_t)L * L && L >= 2 && 2 * tri <= lds;
+  bool ints = have;
+  for (size_t i = 0; ints && i < (size_t)L * L; ++i) ints = d[i] >= 0.f && d[i] <= 65535.f && d[i] == std::floor(d[i]);
+  const bool sym = have && matrix_symmetric();
+  std::vector<uint8_t> t;
+  auto put = [&t](const auto v) {
+    const size_t o = t.size();
+    t.resize(o + sizeof(v));
+    std::memcpy(t.data() + o, &v, sizeof(v));
+  };
+  if (ints && sym) {
+    for (uint32_t i = 0; i < L; ++i)  // rows of the lower triangle with the diagonal: (i, j <= i) at i (i + 1) / 2 + j
+      for (uint32_t j = 0; j <= i; ++j) put((uint16_t)d[(size_t)i * L + j]);
+    aux_kind_ = 1;
+  } else if (ints && 2ull * L * L <= lds) {
+    for (size_t i = 0; i < (size_t)L * L; ++i) put((uint16_t)d[i]);
+    aux_kind_ = 2;
+  } else if (sym && !ints && 4 * tri <= lds) {
+    for (uint32_t i = 0; i < L; ++i)
+      for (uint32_t j = 0; j <= i; ++j) put(d[(size_t)i * L + j]);
+    aux_kind_ = 3;
   }
+  if (aux_kind_) {
+    t.resize((t.size() + 15) / 16 * 16, 0);  // whole 16-byte stores
+    reserve(obj_aux_, t.size());
+    copy_to_device(obj_aux_.ptr, t.data(), t.size());
+    aux_bytes_ = (uint32_t)t.size();
+  }
+}
+
+void Island::prepare_qubo() {
   if (cfg_.objective != OBJ_QUBO) return;
   if (cfg_.encoding != ENC_BINARY) throw std::invalid_argument("the QUBO objective needs the BINARY encoding");
   if (obj_len_[0] < (size_t)cfg_.L * cfg_.L) throw std::invalid_argument("QUBO: objective data must hold the L x L matrix Q");
   if (!on_gpu() || qubo_version_ == obj_version_) return;
   const uint32_t lp = qubo_padded_length(cfg_.L);
   if (lp > kQuboMaxBits) throw std::invalid_argument("QUBO objective supports genomes of at most 1024 bits");
-  if (qubo_qt_.bytes < (size_t)lp * lp) {
-    release(qubo_qt_);
-    release(qubo_qn_);
-    qubo_qt_ = alloc((size_t)lp * lp);
-    qubo_qn_ = alloc((size_t)lp * lp);
-  }
-  qubo_pack_launch((const float*)obj_data_[0].ptr, cfg_.L, (int8_t*)qubo_qt_.ptr, stream, (int8_t*)qubo_qn_.ptr);
+  reserve(qubo_qt_, (size_t)lp * lp);
+  reserve(qubo_qn_, (size_t)lp * lp);
+  qubo_pack_launch(obj_data_[0].as<const float>(), cfg_.L, qubo_qt_.as<int8_t>(), stream, qubo_qn_.as<int8_t>());
   qubo_version_ = obj_version_;
+}
+
+RngKey Island::key() const {
+  return RngKey{(uint32_t)cfg_.seed, (uint32_t)(cfg_.seed >> 32) ^ (epoch_ * 0x9E3779B9u), gen_, cfg_.island};
+}
+
+LsArgs Island::ls_args(int kind, uint32_t moves, float prob) const {
+  if (!(prob == prob)) throw std::invalid_argument("local search probability is NaN");
+  LsArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.rows = rows_[cur_].ptr;
+  a.scores = scores_at(cur_);
+  a.S = cfg_.S;
+  a.L = cfg_.L;
+  a.row_words = row_words_;
+  a.chunks = chunks_;
+  a.key = key();
+  a.objective = cfg_.objective;
+  a.obj_data = obj_data_[0].as<const float>();
+  a.kind = kind;
+  a.moves = moves;
+  a.always = prob >= 1.f ? 1u : 0u;
+  a.thresh = prob_thresh(prob);
+  return a;
 }
 
 bool Island::matrix_symmetric() {
@@ -317,7 +359,7 @@ void Island::local_search(uint32_t moves, float prob) {
   }
   if (cfg_.encoding != ENC_PERMUTATION)
     throw std::invalid_argument("2-opt local search needs the PERMUTATION encoding (one-flip: BINARY with the QUBO objective)");
-  if (jit_) throw std::invalid_argument("2-opt local search needs a built-in TSP objective, not a JIT objective");
+  if (jit_) throw std::invalid_argument(kJitNotTwoOpt);
   const bool euc = cfg_.objective == OBJ_TSP_EUC;
   if (!euc && cfg_.objective != OBJ_TSP && cfg_.objective != OBJ_TSP_OPEN)
     throw std::invalid_argument("2-opt local search needs a built-in TSP objective");
@@ -325,31 +367,13 @@ void Island::local_search(uint32_t moves, float prob) {
     throw std::invalid_argument("2-opt local search: the objective data is not set");
   if (!euc && !matrix_symmetric())
     throw std::invalid_argument("2-opt local search needs a symmetric distance matrix");
-  if (!(prob == prob)) throw std::invalid_argument("local search probability is NaN");
+  LsArgs a = ls_args(LS_TWO_OPT, moves, prob);
   prepare_objective();
-  LsArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.rows = rows_[cur_].ptr;
-  a.scores = (float*)scores_[cur_].ptr;
-  a.S = cfg_.S;
-  a.L = cfg_.L;
-  a.row_words = row_words_;
-  a.chunks = chunks_;
-  a.key.k0 = (uint32_t)cfg_.seed;
-  a.key.k1 = (uint32_t)(cfg_.seed >> 32) ^ (epoch_ * 0x9E3779B9u);
-  a.key.gen = gen_;
-  a.key.island = cfg_.island;
-  a.objective = cfg_.objective;
-  a.obj_data = (const float*)obj_data_[0].ptr;
   if (!euc && aux_kind_ && aux_on_) {
     a.obj_aux = obj_aux_.ptr;
     a.obj_aux_kind = aux_kind_;
     a.obj_aux_bytes = aux_bytes_;
   }
-  a.kind = LS_TWO_OPT;
-  a.moves = moves;
-  a.always = prob >= 1.f ? 1u : 0u;
-  a.thresh = prob_thresh(prob);
   if (on_gpu()) perm_ls_launch(a, stream);
   else cpu::perm_local_search(a);
   // rows and scores changed in place: the partials, the fused statistics and
@@ -358,32 +382,14 @@ void Island::local_search(uint32_t moves, float prob) {
 }
 
 void Island::one_flip_search(uint32_t moves, float prob) {
-  if (jit_) throw std::invalid_argument("one-flip local search needs the built-in QUBO objective, not a JIT objective");
+  if (jit_) throw std::invalid_argument(kJitNotOneFlip);
   if (one_flip_sign(cfg_.obj_f0) == 0)
     throw std::invalid_argument("one-flip local search: the QUBO score factor (obj_f0) must be non-zero");
-  if (!(prob == prob)) throw std::invalid_argument("local search probability is NaN");
+  LsArgs a = ls_args(LS_ONE_FLIP, moves, prob);
   prepare_objective();  // (throws when the matrix is not set) both packed matrices on the GPU
-  LsArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.rows = rows_[cur_].ptr;
-  a.scores = (float*)scores_[cur_].ptr;
-  a.S = cfg_.S;
-  a.L = cfg_.L;
-  a.row_words = row_words_;
-  a.chunks = chunks_;
-  a.key.k0 = (uint32_t)cfg_.seed;
-  a.key.k1 = (uint32_t)(cfg_.seed >> 32) ^ (epoch_ * 0x9E3779B9u);
-  a.key.gen = gen_;
-  a.key.island = cfg_.island;
-  a.objective = cfg_.objective;
-  a.obj_data = (const float*)obj_data_[0].ptr;
-  a.qubo_qt = (const int8_t*)qubo_qt_.ptr;
-  a.qubo_qn = (const int8_t*)qubo_qn_.ptr;
+  a.qubo_qt = qubo_qt_.as<const int8_t>();
+  a.qubo_qn = qubo_qn_.as<const int8_t>();
   a.obj_f0 = cfg_.obj_f0;
-  a.kind = LS_ONE_FLIP;
-  a.moves = moves;
-  a.always = prob >= 1.f ? 1u : 0u;
-  a.thresh = prob_thresh(prob);
   if (on_gpu()) qubo_ls_launch(a, stream);
   else cpu::qubo_local_search(a);
   rebest();  // as after the 2-opt stage
@@ -393,7 +399,7 @@ GenArgs Island::make_args(int mode) {
   prepare_objective();
   GenArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.qubo_qt = (const int8_t*)qubo_qt_.ptr;
+  a.qubo_qt = qubo_qt_.as<const int8_t>();
   if (aux_kind_ && aux_on_ && (cfg_.objective == OBJ_TSP || cfg_.objective == OBJ_TSP_OPEN)) {
     a.obj_aux = obj_aux_.ptr;
     a.obj_aux_kind = aux_kind_;
@@ -404,33 +410,24 @@ GenArgs Island::make_args(int mode) {
     a.knap_dig = knap_dig_;
     a.knap_cols = knap_cols_;
   }
-  const int nx = cur_ ^ 1;
-  a.cur = rows_[cur_].ptr;
-  a.next = rows_[nx].ptr;
-  a.score_cur = (const float*)scores_[cur_].ptr;
-  a.score_next = (float*)scores_[nx].ptr;
-  if (mode == MODE_INIT || mode == MODE_EVAL) {
-    a.next = rows_[cur_].ptr;
-    a.score_next = (float*)scores_[cur_].ptr;
-  } else if (mode == MODE_MUTATE) {
-    a.cur = rows_[nx].ptr;
-    a.next = rows_[nx].ptr;
-  }
+  // INIT and EVAL write the current parity in place, every other mode the next one
+  const int nx = cur_ ^ 1, out = (mode == MODE_INIT || mode == MODE_EVAL) ? cur_ : nx;
+  a.cur = rows_[mode == MODE_MUTATE ? nx : cur_].ptr;
+  a.next = rows_[out].ptr;
+  a.score_cur = scores_at(cur_);
+  a.score_next = scores_at(out);
   a.S = cfg_.S;
   a.L = cfg_.L;
   a.row_words = row_words_;
   a.chunks = chunks_;
   a.encoding = (uint32_t)cfg_.encoding;
-  a.key.k0 = (uint32_t)cfg_.seed;
-  a.key.k1 = (uint32_t)(cfg_.seed >> 32) ^ (epoch_ * 0x9E3779B9u);
-  a.key.gen = gen_;
-  a.key.island = cfg_.island;
+  a.key = key();
   a.selection = cfg_.selection;
   a.tour_k = cfg_.tour_k;
-  a.cumfit = (const float*)cumfit_.ptr;
-  a.roul_guide = (const uint32_t*)roul_guide_.ptr;
-  a.roul_scale = cum_ws_.ptr ? (const float*)cum_ws_.ptr + kRoulScale : nullptr;
-  a.rank_order = (const uint32_t*)rank_order_.ptr;
+  a.cumfit = cumfit_.as<const float>();
+  a.roul_guide = roul_guide_.as<const uint32_t>();
+  a.roul_scale = cum_ws_.ptr ? cum_ws_.as<const float>() + kRoulScale : nullptr;
+  a.rank_order = rank_order_.as<const uint32_t>();
   a.rank_thresh = rank_thresh_of(cfg_.rank_pressure);
   a.crossover = cfg_.crossover;
   a.xo_always = cfg_.xo_prob >= 1.f ? 1u : 0u;
@@ -439,7 +436,7 @@ GenArgs Island::make_args(int mode) {
   a.mutation = cfg_.mutation;
   a.mut_rate = mut_rate_eff_;
   a.mut_ind_thresh = per_individual_mutation(cfg_.mutation) ? prob_thresh(mut_rate_eff_) : 0u;
-  a.mut_thr = (const uint32_t*)mut_thr_.ptr;
+  a.mut_thr = mut_thr_.as<const uint32_t>();
   a.mut_inv_log2_1mp = mut_inv_;
   a.mut_sparse = mut_sparse_ ? 1u : 0u;
   a.sigma = cfg_.sigma;
@@ -449,81 +446,72 @@ GenArgs Island::make_args(int mode) {
   a.obj_i = cfg_.obj_i;
   a.obj_f0 = cfg_.obj_f0;
   a.obj_f1 = cfg_.obj_f1;
-  a.obj_data = (const float*)obj_data_[0].ptr;
-  a.obj_data2 = (const float*)obj_data_[1].ptr;
+  a.obj_data = obj_data_[0].as<const float>();
+  a.obj_data2 = obj_data_[1].as<const float>();
   a.user_fn = user_fn_;
   a.user_xo_fn = user_xo_fn_;
   a.user_mut_fn = user_mut_fn_;
-  a.compat_rand = (float*)compat_rand_.ptr;
+  a.compat_rand = compat_rand_.as<float>();
   a.n_elite = cfg_.n_elite;
-  a.elite_idx = cfg_.n_elite > 1 ? (const uint32_t*)elite_idx_.ptr : nullptr;
-  a.best_cur = (const unsigned long long*)best_[cur_].ptr;
-  a.n_best_cur = n_best_[cur_];
+  a.elite_idx = cfg_.n_elite > 1 ? elite_idx_.as<const uint32_t>() : nullptr;
+  a.best_cur = best_at(cur_);
+  a.n_best_cur = d_[cur_].n_best;
   a.last_mask = last_mask_;
   if (capturing_) {
-    a.gen_dev = (const uint32_t*)gen_dev_.ptr;
+    a.gen_dev = gen_dev_.as<const uint32_t>();
     a.gen_off = gen_ - capture_base_;
   }
-  if (fused_stats()) a.stats_parts = (float*)stats_parts_[(mode == MODE_INIT || mode == MODE_EVAL) ? cur_ : nx].ptr;
+  if (fused_stats()) a.stats_parts = stats_at(out);
   if (integer_objective(cfg_.objective, cfg_.L)) {
-    a.key_cur = (const uint16_t*)keys_[cur_].ptr;
-    a.key_next = (uint16_t*)keys_[nx].ptr;
-    if (mode == MODE_INIT || mode == MODE_EVAL) a.key_next = (uint16_t*)keys_[cur_].ptr;
-  } else if (mode == MODE_GEN && real_qk() && qk_valid_[cur_] && qk_ws_.ptr) {
-    a.key_cur = (const uint16_t*)keys_[cur_].ptr;
-    a.key_next = (uint16_t*)keys_[nx].ptr;
-    a.qk = (const float*)qk_ws_.ptr;
+    a.key_cur = keys_at(cur_);
+    a.key_next = keys_at(out);
+  } else if (mode == MODE_GEN && real_qk() && d_[cur_].qk && qk_ws_.ptr) {
+    a.key_cur = keys_at(cur_);
+    a.key_next = keys_at(nx);
+    a.qk = qk_ws_.as<const float>();
   }
   return a;
 }
 
-uint32_t Island::launch(int mode, const GenArgs& a, unsigned long long* parts) {
-  if (mode != MODE_GEN && a.cur == rows_[cur_].ptr) {  // staged / init / eval
-    fhist_of_[0] = fhist_of_[1] = -1;
-    rank_cnt_of_ = -1;
-  }
+LaunchReport Island::launch(int mode, const GenArgs& a, unsigned long long* parts) {
+  if (mode != MODE_GEN && a.cur == rows_[cur_].ptr) drop_key_counts();  // staged / init / eval
   if (on_gpu()) return encoding_launch(mode, a, parts, stream);
-  return cpu::encoding_run(mode, a, parts);
+  LaunchReport r;
+  r.grid = cpu::encoding_run(mode, a, parts);
+  return r;
 }
 
 void Island::initialize() {
   TraceRange tr("pga.initialize");
-  invalidate_qk();
-  GenArgs a = make_args(MODE_INIT);
-  n_best_[cur_] = launch(MODE_INIT, a, (unsigned long long*)best_[cur_].ptr);
-  set_stats_ok(cur_, a.stats_parts != nullptr);
-  if (jit_) {
-    n_best_[cur_] = jit_eval(rows_[cur_].ptr, (float*)scores_[cur_].ptr, cfg_.S, (unsigned long long*)best_[cur_].ptr);
-    set_stats_ok(cur_, false);
-  } else if (cfg_.objective == OBJ_NONE) {
-    rebest();
-  }
+  evaluate_current(MODE_INIT);
+  if (cfg_.objective == OBJ_NONE && !jit_) rebest();
 }
 
 void Island::evaluate() {
   TraceRange tr("pga.evaluate");
-  invalidate_qk();
-  if (jit_) {
-    n_best_[cur_] = jit_eval(rows_[cur_].ptr, (float*)scores_[cur_].ptr, cfg_.S, (unsigned long long*)best_[cur_].ptr);
-    set_stats_ok(cur_, false);
-    return;
+  evaluate_current(MODE_EVAL);
+}
+
+void Island::evaluate_current(int mode) {
+  Derived made;
+  if (mode == MODE_INIT || !jit_) {
+    GenArgs a = make_args(mode);
+    made.n_best = launch(mode, a, best_at(cur_)).grid;
+    made.stats = a.stats_parts != nullptr;
   }
-  GenArgs a = make_args(MODE_EVAL);
-  n_best_[cur_] = launch(MODE_EVAL, a, (unsigned long long*)best_[cur_].ptr);
-  set_stats_ok(cur_, a.stats_parts != nullptr);
+  if (jit_) made = Derived{jit_eval(rows_[cur_].ptr, scores_at(cur_), cfg_.S, best_at(cur_))};
+  scores_written(cur_, made);
 }
 
 void Island::rebest() {
-  set_stats_ok(cur_, false);
-  invalidate_qk();
-  const float* sc = (const float*)scores_[cur_].ptr;
+  Derived made;
   if (on_gpu()) {
-    uint16_t* keys = integer_objective(cfg_.objective, cfg_.L) ? (uint16_t*)keys_[cur_].ptr : nullptr;
-    n_best_[cur_] = best_of_scores_launch(sc, cfg_.S, (unsigned long long*)best_[cur_].ptr, stream, keys);
+    made.n_best = best_of_scores_launch(scores_at(cur_), cfg_.S, best_at(cur_), stream, int_keys_at(cur_));
   } else {
-    ((unsigned long long*)best_[cur_].ptr)[0] = cpu::best_of_scores(sc, cfg_.S);
-    n_best_[cur_] = 1;
+    best_at(cur_)[0] = cpu::best_of_scores(scores_at(cur_), cfg_.S);
+    made.n_best = 1;
   }
+  scores_written(cur_, made);
 }
 
 bool Island::real_qk() const {
@@ -535,14 +523,12 @@ bool Island::real_qk() const {
 }
 
 void Island::prepare_generation() {
+  const float* sc = scores_at(cur_);
+  const Derived& now = d_[cur_];
   if (real_qk()) {
     // the current generation's score range (fused partials when its kernel
     // stored them), and its quantized keys if anything rewrote the scores
-    if (!qk_ws_.ptr) {
-      qk_ws_ = alloc(4ull * (4 + 3 * 1024));
-      qk_age_ = 0;
-    }
-    const float* sc = (const float*)scores_[cur_].ptr;
+    if (reserve(qk_ws_, 4ull * (4 + 3 * 1024))) qk_age_ = 0;
     // The quantization range only has to be the same for every key of a
     // generation: keys are monotonic in the score and equal keys fall back to
     // the exact f32 compare, so any range gives the same tournaments.  It is
@@ -552,64 +538,54 @@ void Island::prepare_generation() {
     // launch is a larger share of a short generation: reference E1).
     const uint32_t refresh = cfg_.S * batch_n_ < (1ull << 18) ? 32u : 8u;
     if (qk_age_++ % refresh == 0) {
-      if (stats_ok_[cur_])
-        stats_from_parts_launch((const float*)stats_parts_[cur_].ptr, (const unsigned long long*)best_[cur_].ptr,
-                                n_best_[cur_], cfg_.S, (float*)qk_ws_.ptr, stream);
-      else
-        score_stats_launch(sc, cfg_.S, (float*)qk_ws_.ptr, stream);
+      if (now.stats) stats_from_parts_launch(stats_at(cur_), best_at(cur_), now.n_best, cfg_.S, qk_ws_.as<float>(), stream);
+      else score_stats_launch(sc, cfg_.S, qk_ws_.as<float>(), stream);
     }
-    if (!qk_valid_[cur_]) {
-      scores_to_qkeys_launch(sc, cfg_.S, (const float*)qk_ws_.ptr, (uint16_t*)keys_[cur_].ptr, stream);
-      qk_valid_[cur_] = true;
+    if (!now.qk) {
+      scores_to_qkeys_launch(sc, cfg_.S, qk_ws_.as<const float>(), keys_at(cur_), stream);
+      keys_requantized();
     }
   }
   if (cfg_.selection == SEL_ROULETTE) {
-    const float* sc = (const float*)scores_[cur_].ptr;
-    const bool fused = on_gpu() && stats_ok_[cur_] && stats_parts_[cur_].ptr;  // min from the GEN kernel's partials
+    const bool fused = on_gpu() && now.stats && stats_at(cur_);  // min from the GEN kernel's partials
     // integer objectives after a two-phase GEN launch: one exact launch
     // (the partials give every block its carry)
-    const bool one = fused && stats_part_[cur_].grid && integer_objective(cfg_.objective, cfg_.L) &&
+    const bool one = fused && now.part.grid && integer_objective(cfg_.objective, cfg_.L) &&
                      cfg_.objective != OBJ_KNAPSACK && !roul_fused_off() &&
-                     roulette_fused_launch(sc, cfg_.S, (const float*)stats_parts_[cur_].ptr, stats_part_[cur_], cfg_.L,
-                                           (float*)cumfit_.ptr, (uint32_t*)roul_guide_.ptr, (float*)cum_ws_.ptr, stream);
+                     roulette_fused_launch(sc, cfg_.S, stats_at(cur_), now.part, cfg_.L, cumfit_.as<float>(),
+                                           roul_guide_.as<uint32_t>(), cum_ws_.as<float>(), stream);
     if (one) {
     } else if (on_gpu()) {
-      roulette_prefix_launch(sc, cfg_.S, fused ? (const float*)stats_parts_[cur_].ptr : nullptr, n_best_[cur_],
-                             (float*)cumfit_.ptr, (float*)cum_ws_.ptr, stream, integer_objective(cfg_.objective, cfg_.L));
-      roulette_guide_launch((const float*)cumfit_.ptr, cfg_.S, (uint32_t*)roul_guide_.ptr, (float*)cum_ws_.ptr, stream);
+      roulette_prefix_launch(sc, cfg_.S, fused ? stats_at(cur_) : nullptr, now.n_best, cumfit_.as<float>(),
+                             cum_ws_.as<float>(), stream, integer_objective(cfg_.objective, cfg_.L));
+      roulette_guide_launch(cumfit_.as<const float>(), cfg_.S, roul_guide_.as<uint32_t>(), cum_ws_.as<float>(), stream);
     } else {
-      cpu::roulette_prefix(sc, cfg_.S, (float*)cumfit_.ptr);
+      cpu::roulette_prefix(sc, cfg_.S, cumfit_.as<float>());
     }
   }
   if (cfg_.selection == SEL_RANK) {
-    const float* sc = (const float*)scores_[cur_].ptr;
-    if (on_gpu() && integer_objective(cfg_.objective, cfg_.L) && keys_[cur_].ptr) {
-      // the tile counts of these keys, when the GEN kernel that wrote them stored them
-      const bool ready = rank_cnt_of_ == cur_ && !capturing_;
-      rank_cnt_of_ = -1;  // the sort scans them in place
-      rank_order16_launch((const uint16_t*)keys_[cur_].ptr, cfg_.S, cfg_.L + 1, (uint32_t*)rank_order_.ptr,
-                          rank_ws_.ptr, stream, ready);
+    uint32_t* order = rank_order_.as<uint32_t>();
+    if (on_gpu() && int_keys_at(cur_)) {
+      // with the tile counts of these keys, when the GEN kernel that wrote them stored them
+      rank_order16_launch(keys_at(cur_), cfg_.S, cfg_.L + 1, order, rank_ws_.ptr, stream, take_rank_counts());
     }
-    else if (on_gpu()) rank_order_launch(sc, cfg_.S, (uint32_t*)rank_order_.ptr, rank_ws_.ptr, stream);
-    else cpu::rank_order(sc, cfg_.S, (uint32_t*)rank_order_.ptr);
+    else if (on_gpu()) rank_order_launch(sc, cfg_.S, order, rank_ws_.ptr, stream);
+    else cpu::rank_order(sc, cfg_.S, order);
   }
-  if (cfg_.n_elite > 1) topk(cfg_.n_elite, true, (uint32_t*)elite_idx_.ptr, /*sorted=*/false);
+  if (cfg_.n_elite > 1) topk(cfg_.n_elite, true, elite_idx_.as<uint32_t>(), /*sorted=*/false);
 }
 
 void Island::run(uint32_t n) {
   TraceRange tr("pga.run");
   if (cfg_.local_search != LS_NONE) {  // a stage follows every generation: plain launches only
-    if (jit_)
-      throw std::invalid_argument(cfg_.local_search == LS_ONE_FLIP
-                                      ? "one-flip local search needs the built-in QUBO objective, not a JIT objective"
-                                      : "2-opt local search needs a built-in TSP objective, not a JIT objective");
+    if (jit_) throw std::invalid_argument(cfg_.local_search == LS_ONE_FLIP ? kJitNotOneFlip : kJitNotTwoOpt);
     run_plain(n);
     return;
   }
   if (run_tiny(n)) return;
   if (on_gpu() && graph_g_ > 0 && !graph_broken_ && !hist_on_ && n >= graph_g_ + 2) {
     const bool fresh = gexec_ && g_cur_ == cur_ && g_epoch_ == epoch_ && g_version_ == version_ &&
-                       g_nbest_ == n_best_[cur_] && g_len_ == graph_g_;
+                       g_nbest_ == d_[cur_].n_best && g_len_ == graph_g_;
     if (!fresh) {
       // two plain generations first: the best-partials count of this parity
       // then equals the GEN kernel's grid, which is what every replay leaves
@@ -617,8 +593,7 @@ void Island::run(uint32_t n) {
       n -= 2;
     }
     const uint32_t reps = n / graph_g_;
-    fhist_of_[0] = fhist_of_[1] = -1;  // replays do not produce the fused histograms
-    rank_cnt_of_ = -1;                 // (nor rank counts; their sorts overwrite the workspace)
+    drop_key_counts();  // replays produce no fused histogram (nor rank counts; their sorts overwrite the workspace)
     if (run_graph(reps, fresh)) n -= reps * graph_g_;
   }
   run_plain(n);
@@ -632,8 +607,8 @@ bool Island::run_tiny(uint32_t n) {
   if (cfg_.n_elite > 1 || (cfg_.selection != SEL_TOURNAMENT && cfg_.selection != SEL_RANDOM)) return false;
   GenArgs a = make_args(MODE_GEN);
   const int nx = cur_ ^ 1;
-  unsigned long long* const parts[2] = {(unsigned long long*)best_[nx].ptr, (unsigned long long*)best_[cur_].ptr};
-  float* const st[2] = {a.stats_parts, a.stats_parts ? (float*)stats_parts_[cur_].ptr : nullptr};
+  unsigned long long* const parts[2] = {best_at(nx), best_at(cur_)};
+  float* const st[2] = {a.stats_parts, a.stats_parts ? stats_at(cur_) : nullptr};
   if (!real_launch_multi(a, parts, st, n, stream)) return false;
   TraceRange tg("pga.generations_tiny", 2);
   // the kernel keeps the population in LDS between generations: only the
@@ -641,11 +616,10 @@ bool Island::run_tiny(uint32_t n) {
   for (uint32_t i = 0; i < n; ++i) swap();
   // the previous parity's rows / scores / partials were never written (its
   // generations lived in LDS): no valid partials there until a kernel writes them
-  n_best_[cur_] = 1;
-  n_best_[cur_ ^ 1] = 0;
-  set_stats_ok(cur_, a.stats_parts != nullptr);
-  set_stats_ok(cur_ ^ 1, false);
-  qk_valid_[0] = qk_valid_[1] = false;
+  Derived made{1};
+  made.stats = a.stats_parts != nullptr;
+  scores_written(cur_, made);
+  scores_written(cur_ ^ 1, Derived{});
   return true;
 }
 
@@ -654,45 +628,30 @@ void Island::run_plain(uint32_t n) {
     TraceRange tg("pga.generation", 2);
     prepare_generation();
     GenArgs a = make_args(MODE_GEN);
-    if (jit_ && fused_jit_generation(a)) {  // the objective linked into the generation kernel
-      rank_cnt_of_ = -1;
-      swap();
-      if (hist_on_ && !hist_manual_ && !capturing_) append_history();
-      continue;
-    }
-    bool fh = fhist_ready_for(a);
-    if (fh) {  // this generation may also write the value histogram of its keys (GenArgs::key_hist)
-      a.key_hist = (uint32_t*)fhist_[fhist_rot_ % 3].ptr;
-      a.hist_zero = (uint32_t*)fhist_[(fhist_rot_ + 1) % 3].ptr;
-      a.hist_bins = cfg_.L + 1;
-      a.hist_zero_words = fused_hist_words(cfg_.L + 1);
-    }
-    a.rank_counts = rank_counts_for_gen();
-    if (a.rank_counts) a.hist_bins = cfg_.L + 1;
-    n_best_[cur_ ^ 1] = launch(MODE_GEN, a, (unsigned long long*)best_[cur_ ^ 1].ptr);
-    set_stats_ok(cur_ ^ 1, a.stats_parts != nullptr);
-    tp_tail_ = cfg_.encoding == ENC_BINARY && on_gpu() ? binary_tp_partition().tail : 0u;
-    if (a.stats_parts && cfg_.encoding == ENC_BINARY && on_gpu() && binary_tp_partition().grid == n_best_[cur_ ^ 1])
-      stats_part_[cur_ ^ 1] = binary_tp_partition();  // (the roulette prefix's carries, roulette_fused_launch)
-    rank_cnt_of_ = a.rank_counts && binary_rank_counts_written() ? (cur_ ^ 1) : -1;
-    // valid only when the launcher reports that its kernel took the histogram
-    // (binary_gs.hip go_tp), not on the conditions predicted above
-    fh = fh && binary_hist_written();
-    if (fh) {
-      const int w = (int)(fhist_rot_ % 3), z = (int)((fhist_rot_ + 1) % 3);
-      ++fhist_rot_;
-      fhist_of_[cur_ ^ 1] = w;
-      fhist_clean_[w] = true;   // zeroed (bins and status) by the launch before this one
-      fhist_clean_[z] = true;   // zeroed by this launch
-      if (fhist_of_[cur_] == z) fhist_of_[cur_] = -1;
-    } else {
-      fhist_of_[cur_ ^ 1] = -1;
-    }
-    qk_valid_[cur_ ^ 1] = a.qk != nullptr && !jit_;  // every REAL GEN kernel writes the keys it is given
-    if (jit_) {
-      n_best_[cur_ ^ 1] = jit_eval(rows_[cur_ ^ 1].ptr, (float*)scores_[cur_ ^ 1].ptr, cfg_.S,
-                                   (unsigned long long*)best_[cur_ ^ 1].ptr);
-      set_stats_ok(cur_ ^ 1, false);
+    if (!jit_ || !fused_jit_generation(a)) {  // (else: the objective linked into the generation kernel)
+      const int nx = cur_ ^ 1, w = (int)(fhist_rot_ % 3);
+      const bool fh = fhist_ready_for(a);
+      if (fh) {  // this generation may also write the value histogram of its keys (GenArgs::key_hist)
+        a.key_hist = fhist_[w].as<uint32_t>();
+        a.hist_zero = fhist_[(w + 1) % 3].as<uint32_t>();
+        a.hist_bins = cfg_.L + 1;
+        a.hist_zero_words = fused_hist_words(cfg_.L + 1);
+      }
+      a.rank_counts = rank_counts_for_gen();
+      if (a.rank_counts) a.hist_bins = cfg_.L + 1;
+      const LaunchReport rep = launch(MODE_GEN, a, best_at(nx));
+      tp_tail_ = rep.part.tail;
+      Derived made{rep.grid};
+      made.stats = a.stats_parts != nullptr;
+      // (the roulette prefix's carries, roulette_fused_launch)
+      if (made.stats && rep.part.grid == rep.grid) made.part = rep.part;
+      made.qk = a.qk != nullptr;  // every REAL GEN kernel writes the keys it is given
+      // the histogram and the rank counts only when the launcher reports that its
+      // kernel took them (binary_gs.hip go_tp), not on the conditions predicted above
+      if (fh && rep.hist) made.fhist = w;
+      made.rank_cnt = a.rank_counts && rep.rank_counts;
+      if (jit_) made = Derived{jit_eval(rows_[nx].ptr, scores_at(nx), cfg_.S, best_at(nx))};
+      scores_written(nx, made);
     }
     swap();
     if (cfg_.local_search != LS_NONE) local_search(cfg_.ls_moves, cfg_.ls_prob);
@@ -760,24 +719,24 @@ bool Island::run_batched(const std::vector<Island*>& isls, uint32_t n, hipStream
       I.stream = s;
       I.prepare_generation();
       args[k] = I.make_args(MODE_GEN);
-      parts[k] = (unsigned long long*)I.best_[I.cur_ ^ 1].ptr;
+      parts[k] = I.best_at(I.cur_ ^ 1);
     }
-    const uint32_t grid = bin    ? binary_launch_batch(args.data(), parts.data(), (uint32_t)N, s)
-                          : real ? real_launch_batch(args.data(), parts.data(), (uint32_t)N, s)
-                                 : perm_launch_batch(args.data(), parts.data(), (uint32_t)N, s);
-    if (grid == 0) {
+    LaunchReport rep;  // (REAL and PERMUTATION report their grid alone)
+    if (bin) rep = binary_launch_batch(args.data(), parts.data(), (uint32_t)N, s);
+    else rep.grid = real ? real_launch_batch(args.data(), parts.data(), (uint32_t)N, s)
+                         : perm_launch_batch(args.data(), parts.data(), (uint32_t)N, s);
+    if (rep.grid == 0) {
       if (g == 0) return false;  // not eligible (decided on the first generation's arguments)
       throw std::logic_error("batched islands stopped qualifying mid-run");
     }
     for (size_t k = 0; k < N; ++k) {
       Island& I = *isls[k];
-      const int nx = I.cur_ ^ 1;
-      I.n_best_[nx] = grid;
-      I.set_stats_ok(nx, args[k].stats_parts != nullptr);
-      I.qk_valid_[nx] = real && args[k].qk != nullptr;  // the REAL kernel writes the keys it is given
-      I.fhist_of_[nx] = -1;  // the batched launch produces no fused histogram
-      I.rank_cnt_of_ = -1;
-      I.tp_tail_ = bin ? binary_tp_partition().tail : 0u;
+      // no fused histogram, rank counts or roulette partition from the batched launch
+      Derived made{rep.grid};
+      made.stats = args[k].stats_parts != nullptr;
+      made.qk = real && args[k].qk != nullptr;  // the REAL kernel writes the keys it is given
+      I.scores_written(I.cur_ ^ 1, made);
+      I.tp_tail_ = rep.part.tail;
       I.swap();
     }
   }
@@ -812,25 +771,23 @@ void Island::set_stats_history(bool on) {
 void Island::append_history() {
   if (!on_gpu()) {
     float r[4];
-    cpu::score_stats((const float*)scores_[cur_].ptr, cfg_.S, r);
+    cpu::score_stats(scores_at(cur_), cfg_.S, r);
     hist_host_.insert(hist_host_.end(), r, r + 4);
     ++hist_n_;
     return;
   }
   if (hist_.bytes < 16ull * (hist_n_ + 1)) {  // grow (rare): keep the rows so far
     const uint64_t cap = std::max<uint64_t>(1024, 2 * (hist_n_ + 1));
-    Buffer nb = alloc(16ull * cap);
+    Buffer nb(16ull * cap, true);
     if (hist_n_) PGA_HIP_CHECK(hipMemcpyAsync(nb.ptr, hist_.ptr, 16ull * hist_n_, hipMemcpyDeviceToDevice, stream));
     synchronize();
-    release(hist_);
-    hist_ = nb;
+    hist_ = std::move(nb);  // (nb frees the old rows)
   }
-  float* row = (float*)hist_.ptr + 4 * hist_n_;
-  if (stats_ok_[cur_]) {
-    stats_from_parts_launch((const float*)stats_parts_[cur_].ptr, (const unsigned long long*)best_[cur_].ptr,
-                            n_best_[cur_], cfg_.S, row, stream);
+  float* row = hist_.as<float>() + 4 * hist_n_;
+  if (d_[cur_].stats) {
+    stats_from_parts_launch(stats_at(cur_), best_at(cur_), d_[cur_].n_best, cfg_.S, row, stream);
   } else {
-    score_stats_launch((const float*)scores_[cur_].ptr, cfg_.S, (float*)stats_.ptr, stream);
+    score_stats_launch(scores_at(cur_), cfg_.S, stats_.as<float>(), stream);
     PGA_HIP_CHECK(hipMemcpyAsync(row, stats_.ptr, 16, hipMemcpyDeviceToDevice, stream));
   }
   ++hist_n_;
@@ -864,23 +821,21 @@ void Island::swap() {
 unsigned long long Island::best_packed() {
   unsigned long long r = 0;
   if (on_gpu()) {
-    reduce_best_launch((const unsigned long long*)best_[cur_].ptr, n_best_[cur_], (unsigned long long*)out_best_.ptr,
-                       stream);
+    reduce_best_launch(best_at(cur_), d_[cur_].n_best, out_best_.as<unsigned long long>(), stream);
     copy_to_host(&r, out_best_.ptr, 8);
   } else {
-    r = cpu::reduce_best((const unsigned long long*)best_[cur_].ptr, n_best_[cur_]);
+    r = cpu::reduce_best(best_at(cur_), d_[cur_].n_best);
   }
   return r;
 }
 
 void Island::stats(float out[4]) {
-  const float* sc = (const float*)scores_[cur_].ptr;
-  if (on_gpu() && stats_ok_[cur_]) {  // fused partials of the kernel that scored this generation
-    stats_from_parts_launch((const float*)stats_parts_[cur_].ptr, (const unsigned long long*)best_[cur_].ptr,
-                            n_best_[cur_], cfg_.S, (float*)stats_.ptr, stream);
+  const float* sc = scores_at(cur_);
+  if (on_gpu() && d_[cur_].stats) {  // fused partials of the kernel that scored this generation
+    stats_from_parts_launch(stats_at(cur_), best_at(cur_), d_[cur_].n_best, cfg_.S, stats_.as<float>(), stream);
     copy_to_host(out, stats_.ptr, 16);
   } else if (on_gpu()) {
-    score_stats_launch(sc, cfg_.S, (float*)stats_.ptr, stream);
+    score_stats_launch(sc, cfg_.S, stats_.as<float>(), stream);
     copy_to_host(out, stats_.ptr, 16);
   } else {
     cpu::score_stats(sc, cfg_.S, out);
@@ -889,20 +844,17 @@ void Island::stats(float out[4]) {
 
 void Island::ensure_topk_ws(uint32_t k) {
   const size_t need = topk_workspace_bytes(cfg_.S, k);
-  if (topk_ws_.bytes >= need) return;
-  synchronize();
-  release(topk_ws_);
-  topk_ws_ = alloc(need);
-  PGA_HIP_CHECK(hipMemsetAsync(topk_ws_.ptr, 0, need, stream));  // the value histogram must start zeroed
+  if (reserve(topk_ws_, need, /*sync=*/true))
+    PGA_HIP_CHECK(hipMemsetAsync(topk_ws_.ptr, 0, need, stream));  // the value histogram must start zeroed
 }
 
 void Island::topk(uint32_t k, bool largest, uint32_t* idx_out, bool sorted) {
   TraceRange tr(largest ? "pga.topk" : "pga.bottomk");
   if (k > cfg_.S) throw std::invalid_argument("k exceeds population size");
-  const float* sc = (const float*)scores_[cur_].ptr;
+  const float* sc = scores_at(cur_);
   if (on_gpu()) {
     ensure_topk_ws(k);
-    const uint16_t* k16 = integer_objective(cfg_.objective, cfg_.L) ? (const uint16_t*)keys_[cur_].ptr : nullptr;
+    const uint16_t* k16 = int_keys_at(cur_);
     TopkFused f;
     topk_launch(sc, k16, cfg_.L + 1, cfg_.S, k, largest, sorted, idx_out, topk_ws_.ptr, stream, nullptr,
                 sorted || !k16 ? nullptr : fused_select(f));
@@ -933,7 +885,7 @@ std::vector<uint32_t> Island::row_host(uint64_t i) {
 
 bool Island::qkeys_host(int which, std::vector<uint16_t>& keys, float range[2]) {
   const int p = (which & 1) ^ cur_;
-  if (!real_qk() || !qk_valid_[p] || !qk_ws_.ptr || !keys_[p].ptr) return false;
+  if (!real_qk() || !d_[p].qk || !qk_ws_.ptr || !keys_[p].ptr) return false;
   keys.resize(cfg_.S);
   copy_to_host(keys.data(), keys_[p].ptr, 2ull * cfg_.S);
   copy_to_host(range, qk_ws_.ptr, 8);
@@ -943,18 +895,17 @@ bool Island::qkeys_host(int which, std::vector<uint16_t>& keys, float range[2]) 
 void Island::gather(const uint32_t* idx, uint32_t n, void* out_rows, float* out_scores) {
   TraceRange tr("pga.migrate.gather");
   if (on_gpu())
-    gather_rows_launch(rows_[cur_].ptr, (const float*)scores_[cur_].ptr, row_words_, idx, n, out_rows, out_scores,
-                       stream);
+    gather_rows_launch(rows_[cur_].ptr, scores_at(cur_), row_words_, idx, n, out_rows, out_scores, stream);
   else
-    cpu::gather_rows(rows_[cur_].ptr, (const float*)scores_[cur_].ptr, row_words_, idx, n, out_rows, out_scores);
+    cpu::gather_rows(rows_[cur_].ptr, scores_at(cur_), row_words_, idx, n, out_rows, out_scores);
 }
 
 void Island::scatter(const uint32_t* idx, uint32_t n, const void* in_rows, const float* in_scores) {
   TraceRange tr("pga.migrate.scatter");
   if (on_gpu())
-    scatter_rows_launch(rows_[cur_].ptr, (float*)scores_[cur_].ptr, row_words_, idx, n, in_rows, in_scores, stream);
+    scatter_rows_launch(rows_[cur_].ptr, scores_at(cur_), row_words_, idx, n, in_rows, in_scores, stream);
   else
-    cpu::scatter_rows(rows_[cur_].ptr, (float*)scores_[cur_].ptr, row_words_, idx, n, in_rows, in_scores);
+    cpu::scatter_rows(rows_[cur_].ptr, scores_at(cur_), row_words_, idx, n, in_rows, in_scores);
   rebest();  // best partials and tournament keys follow the new scores
 }
 
@@ -969,26 +920,24 @@ void Island::emigrate(uint32_t k, void* out_rows, float* out_scores) {
   if (k > cfg_.S) throw std::invalid_argument("k exceeds population size");
   if (mig_policy_ == MIG_STRIPE) {
     if (on_gpu())
-      stripe_emigrate_launch((const float*)scores_[cur_].ptr, rows_[cur_].ptr, row_words_, cfg_.S, k, out_rows,
-                             out_scores, stream);
+      stripe_emigrate_launch(scores_at(cur_), rows_[cur_].ptr, row_words_, cfg_.S, k, out_rows, out_scores, stream);
     else
-      cpu::stripe_emigrate((const float*)scores_[cur_].ptr, rows_[cur_].ptr, row_words_, cfg_.S, k, out_rows,
-                           out_scores);
+      cpu::stripe_emigrate(scores_at(cur_), rows_[cur_].ptr, row_words_, cfg_.S, k, out_rows, out_scores);
     return;
   }
-  const uint16_t* k16 = integer_objective(cfg_.objective, cfg_.L) ? (const uint16_t*)keys_[cur_].ptr : nullptr;
+  const uint16_t* k16 = int_keys_at(cur_);
   if (on_gpu() && topk_move_supported(k16, cfg_.L + 1, cfg_.S)) {
     ensure_topk_ws(k);
     TopkMove mv;
     mv.mode = TopkMove::GATHER;
     mv.rw16 = row_words_ / 4;
-    mv.src_rows = (const uint4*)rows_[cur_].ptr;
-    mv.src_scores = (const float*)scores_[cur_].ptr;
+    mv.src_rows = rows_[cur_].as<const uint4>();
+    mv.src_scores = scores_at(cur_);
     mv.dst_rows = (uint4*)out_rows;
     mv.dst_scores = out_scores;
     TopkFused f;
-    topk_launch((const float*)scores_[cur_].ptr, k16, cfg_.L + 1, cfg_.S, k, true, false, nullptr, topk_ws_.ptr, stream,
-                &mv, fused_select(f));
+    topk_launch(scores_at(cur_), k16, cfg_.L + 1, cfg_.S, k, true, false, nullptr, topk_ws_.ptr, stream, &mv,
+                fused_select(f));
     return;
   }
   uint32_t* idx = (uint32_t*)scratch(4ull * k);
@@ -999,20 +948,18 @@ void Island::emigrate(uint32_t k, void* out_rows, float* out_scores) {
 void Island::immigrate(uint32_t k, const void* in_rows, const float* in_scores) {
   TraceRange tr("pga.migrate.immigrate");
   if (k == 0) return;
-  TopkFused f;
-  const TopkFused* fsel = fused_select(f);  // the victims' selection, before the keys change
-  invalidate_qk();
   if (k > cfg_.S) throw std::invalid_argument("k exceeds population size");
-  uint16_t* k16 = integer_objective(cfg_.objective, cfg_.L) ? (uint16_t*)keys_[cur_].ptr : nullptr;
+  uint16_t* k16 = int_keys_at(cur_);
   if (mig_policy_ == MIG_STRIPE) {
     if (on_gpu()) {
       // victims, their keys, and the island's best partials + statistics in one pass
-      float* sp = fused_stats() ? (float*)stats_parts_[cur_].ptr : nullptr;
-      n_best_[cur_] = stripe_immigrate_launch((float*)scores_[cur_].ptr, k16, rows_[cur_].ptr, row_words_, cfg_.S, k,
-                                              in_rows, in_scores, (unsigned long long*)best_[cur_].ptr, sp, stream);
-      set_stats_ok(cur_, sp != nullptr);
+      float* sp = fused_stats() ? stats_at(cur_) : nullptr;
+      Derived made{stripe_immigrate_launch(scores_at(cur_), k16, rows_[cur_].ptr, row_words_, cfg_.S, k, in_rows,
+                                           in_scores, best_at(cur_), sp, stream)};
+      made.stats = sp != nullptr;
+      scores_written(cur_, made);
     } else {
-      cpu::stripe_immigrate((float*)scores_[cur_].ptr, rows_[cur_].ptr, row_words_, cfg_.S, k, in_rows, in_scores);
+      cpu::stripe_immigrate(scores_at(cur_), rows_[cur_].ptr, row_words_, cfg_.S, k, in_rows, in_scores);
       rebest();
     }
     return;
@@ -1024,18 +971,16 @@ void Island::immigrate(uint32_t k, const void* in_rows, const float* in_scores) 
     mv.rw16 = row_words_ / 4;
     mv.src_rows = (const uint4*)in_rows;
     mv.src_scores = in_scores;
-    mv.dst_rows = (uint4*)rows_[cur_].ptr;
-    mv.dst_scores = (float*)scores_[cur_].ptr;
+    mv.dst_rows = rows_[cur_].as<uint4>();
+    mv.dst_scores = scores_at(cur_);
     mv.dst_keys = k16;
-    mv.best_parts = (unsigned long long*)best_[cur_].ptr;  // the new per-block bests, from the selection itself
-    const uint32_t nb = topk_launch((const float*)scores_[cur_].ptr, k16, cfg_.L + 1, cfg_.S, k, false, false,
-                                    nullptr, topk_ws_.ptr, stream, &mv, fsel);
+    mv.best_parts = best_at(cur_);  // the new per-block bests, from the selection itself
+    TopkFused f;  // the victims' selection reads the histogram of the keys as they are before it
+    const uint32_t nb = topk_launch(scores_at(cur_), k16, cfg_.L + 1, cfg_.S, k, false, false, nullptr, topk_ws_.ptr,
+                                    stream, &mv, fused_select(f));
     // the victims' keys were written with their rows; the best partials came
     // with the selection (else one pass over the scores)
-    n_best_[cur_] = nb ? nb
-                       : best_of_scores_launch((const float*)scores_[cur_].ptr, cfg_.S,
-                                               (unsigned long long*)best_[cur_].ptr, stream, nullptr);
-    set_stats_ok(cur_, false);
+    scores_written(cur_, Derived{nb ? nb : best_of_scores_launch(scores_at(cur_), cfg_.S, best_at(cur_), stream, nullptr)});
     return;
   }
   uint32_t* idx = (uint32_t*)scratch(4ull * k);
@@ -1048,28 +993,17 @@ void Island::set_fused_histogram(bool on) {
   fhist_on_ = on || cfg_.n_elite > 1;
 }
 
-bool Island::roul_fused_off() {
-  static const bool off = [] {
-    const char* e = std::getenv("PGA_ROUL_FUSED");
-    return e && e[0] == '0';
-  }();
-  return off;
-}
-
 uint32_t* Island::rank_counts_for_gen() const {
   // the launcher (binary_gs.hip go_tp) takes them only at the sort's tile geometry
   if (cfg_.selection != SEL_RANK || !on_gpu() || capturing_ || jit_ || cfg_.encoding != ENC_BINARY) return nullptr;
   if (!integer_objective(cfg_.objective, cfg_.L) || cfg_.objective == OBJ_KNAPSACK || !keys_[0].ptr) return nullptr;
   if (cfg_.L + 1 > kHistMaxBins || !rank_ws_.ptr) return nullptr;
-  static const bool off = [] {  // PGA_RANK_FUSED=0: the sort counts its keys itself (A/B knob)
-    const char* e = std::getenv("PGA_RANK_FUSED");
-    return e && e[0] == '0';
-  }();
+  static const bool off = env_off("PGA_RANK_FUSED");  // the sort counts its keys itself
   if (off) return nullptr;
   return rank_order16_counts(rank_ws_.ptr, cfg_.S, cfg_.L + 1);
 }
 
-bool Island::fhist_ready_for(const GenArgs& a) const {
+bool Island::fhist_ready_for(const GenArgs& a) {
   // the conditions under which binary_gen_tp runs with u16 keys (binary_gs.hip
   // launch_mode), so the launch really produces the histogram
   if (!fhist_on_ || !on_gpu() || capturing_ || jit_ || cfg_.encoding != ENC_BINARY) return false;
@@ -1078,21 +1012,16 @@ bool Island::fhist_ready_for(const GenArgs& a) const {
   uint32_t gs = 0;
   bool full = false, dense = false;
   if (!binary_tp_plan(a, gs, full, dense)) return false;
-  if (!fhist_[0].ptr) {  // allocated zeroed on first use
-    Island* self = const_cast<Island*>(this);
-    for (auto& b : self->fhist_) {
-      b = self->alloc(4ull * fused_hist_words(cfg_.L + 1));
-      PGA_HIP_CHECK(hipMemsetAsync(b.ptr, 0, b.bytes, stream));
-    }
-  }
+  for (Buffer& b : fhist_)  // allocated zeroed on first use
+    if (reserve(b, 4ull * fused_hist_words(cfg_.L + 1))) PGA_HIP_CHECK(hipMemsetAsync(b.ptr, 0, b.bytes, stream));
   return true;
 }
 
 const TopkFused* Island::fused_select(TopkFused& f) {
-  const int b = on_gpu() ? fhist_of_[cur_] : -1;
+  const int b = on_gpu() ? d_[cur_].fhist : -1;
   if (b < 0) return nullptr;
-  f.hist = (const uint32_t*)fhist_[b].ptr;
-  f.status = (uint32_t*)fhist_[b].ptr + (cfg_.L + 1 + 3) / 4 * 4;
+  f.hist = fhist_[b].as<const uint32_t>();
+  f.status = fhist_[b].as<uint32_t>() + (cfg_.L + 1 + 3) / 4 * 4;
   if (!fhist_clean_[b])  // a selection on this population already used its status words
     PGA_HIP_CHECK(hipMemsetAsync(f.status, 0, 4ull * kTopkStatusWords, stream));
   fhist_clean_[b] = false;
@@ -1103,9 +1032,9 @@ bool Island::evaluate_rows(void* rows, float* scores, uint32_t n) {
   if (cfg_.objective == OBJ_NONE && !jit_) return false;
   if (n == 0) return true;
   TraceRange tr("pga.migrate.evaluate");
-  if (!ev_parts_.ptr) ev_parts_ = alloc(8ull * kMaxGrid);
+  reserve(ev_parts_, 8ull * kMaxGrid);
   if (jit_) {
-    jit_eval(rows, scores, n, (unsigned long long*)ev_parts_.ptr);
+    jit_eval(rows, scores, n, ev_parts_.as<unsigned long long>());
     return true;
   }
   GenArgs a = make_args(MODE_EVAL);
@@ -1119,7 +1048,7 @@ bool Island::evaluate_rows(void* rows, float* scores, uint32_t n) {
   a.stats_parts = nullptr;  // the island's own statistics are not these rows'
   a.n_elite = 0;
   a.elite_idx = nullptr;
-  launch(MODE_EVAL, a, (unsigned long long*)ev_parts_.ptr);
+  launch(MODE_EVAL, a, ev_parts_.as<unsigned long long>());
   return true;
 }
 
@@ -1133,7 +1062,7 @@ void Island::set_jit_objective(std::shared_ptr<JitKernel> k) {
   }
   jit_ = std::move(k);
   jit_fused_off_ = false;
-  invalidate();
+  config_changed();
 }
 
 bool Island::fused_jit_generation(GenArgs& a) {
@@ -1150,18 +1079,17 @@ bool Island::fused_jit_generation(GenArgs& a) {
   }
   TraceRange tr("pga.jit_generation", 2);
   const int nx = cur_ ^ 1;
-  a.stats_parts = (float*)stats_parts_[nx].ptr;  // the fused kernel stores {min, sum} partials like the built-ins
-  n_best_[nx] = jit_->gen_launch(f, &a, sizeof(a), cfg_.S, (unsigned long long*)best_[nx].ptr, kMaxGrid, stream);
-  set_stats_ok(nx, a.stats_parts != nullptr);
-  qk_valid_[nx] = false;
+  a.stats_parts = stats_at(nx);  // the fused kernel stores {min, sum} partials like the built-ins
+  Derived made{jit_->gen_launch(f, &a, sizeof(a), cfg_.S, best_at(nx), kMaxGrid, stream)};
+  made.stats = a.stats_parts != nullptr;
+  scores_written(nx, made);
   ++jit_fused_gens_;
   return true;
 }
 
 uint32_t Island::jit_eval(const void* rows, float* scores, uint64_t n, unsigned long long* parts) {
   TraceRange tr("pga.jit_eval", 2);
-  return jit_->eval(device_, rows, row_words_, n, cfg_.L, (const float*)obj_data_[0].ptr, scores, parts, kMaxGrid,
-                    stream);
+  return jit_->eval(device_, rows, row_words_, n, cfg_.L, obj_data_[0].as<const float>(), scores, parts, kMaxGrid, stream);
 }
 
 // ------------------------------------------------------------ hipGraph ---
@@ -1179,14 +1107,14 @@ void Island::drop_graph() {
 
 bool Island::capture_graph() {
   drop_graph();
-  if (!gen_dev_.ptr) gen_dev_ = alloc(64);
+  reserve(gen_dev_, 64);
   if (!cap_stream_) PGA_HIP_CHECK(hipStreamCreateWithFlags(&cap_stream_, hipStreamNonBlocking));
   // workspaces that a stage would otherwise (re)allocate synchronously
   if (cfg_.n_elite > 1) {
     ensure_topk_ws(cfg_.n_elite);
   }
   const int cur0 = cur_;
-  const uint32_t gen0 = gen_, nb0 = n_best_[cur_];
+  const uint32_t gen0 = gen_, nb0 = d_[cur_].n_best;
   hipStream_t user = stream;
   stream = cap_stream_;
   capturing_ = true;
@@ -1196,7 +1124,7 @@ bool Island::capture_graph() {
   if (ok) {
     try {
       run_plain(graph_g_);
-      advance_counter_launch((uint32_t*)gen_dev_.ptr, graph_g_, cap_stream_);
+      advance_counter_launch(gen_dev_.as<uint32_t>(), graph_g_, cap_stream_);
     } catch (...) {
       ok = false;
     }
@@ -1270,7 +1198,7 @@ void Island::save(const std::string& path) {
 
 void Island::load(const std::string& path) {
   TraceRange tr("pga.checkpoint.load");
-  invalidate();
+  config_changed();
   FILE* f = std::fopen(path.c_str(), "rb");
   if (!f) throw std::runtime_error("cannot open checkpoint: " + path);
   CkptHeader h;

@@ -16,6 +16,7 @@
 
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "pga/core.hpp"
@@ -59,9 +60,33 @@ struct Config {
 // words per row and gene chunks for an encoding
 void row_geometry(int32_t encoding, uint32_t L, uint32_t* row_words, uint32_t* chunks);
 
+// Owning, move-only memory: hipMalloc on the device, or 64-byte aligned and
+// zeroed on the host, chosen when it is allocated.  The destructor frees it and
+// swallows errors.
 struct Buffer {
   void* ptr = nullptr;
   size_t bytes = 0;
+
+  Buffer() = default;
+  Buffer(size_t n, bool device);
+  Buffer(Buffer&& o) noexcept : ptr(o.ptr), bytes(o.bytes), device_(o.device_) { o.ptr = nullptr, o.bytes = 0; }
+  Buffer& operator=(Buffer&& o) noexcept {
+    std::swap(ptr, o.ptr), std::swap(bytes, o.bytes), std::swap(device_, o.device_);  // o frees the old memory
+    return *this;
+  }
+  ~Buffer();
+  // grow-only: a fresh allocation of n bytes (the contents are not kept) when
+  // fewer are held; true when it reallocated
+  bool reserve(size_t n, bool device) {
+    if (bytes >= n) return false;
+    *this = Buffer(n, device);
+    return true;
+  }
+  template <typename T>
+  T* as() const { return (T*)ptr; }
+
+ private:
+  bool device_ = false;
 };
 
 class Island {
@@ -89,7 +114,7 @@ class Island {
   void set_objective_data(const float* host, size_t n, int which);  // which = 0 or 1
   void set_user_fn(void* f) {
     user_fn_ = f;
-    invalidate();
+    config_changed();
   }
   // reference-ABI crossover_f / mutate_f device pointers (nullptr = built-in)
   void set_user_operators(void* xo, void* mut);
@@ -188,17 +213,14 @@ class Island {
   void set_fused_histogram(bool on);
   bool fused_histogram() const { return fhist_on_; }
   // a fused histogram of the current population is available (tests, benches)
-  bool fused_histogram_ready() const { return fhist_of_[cur_] >= 0; }
+  bool fused_histogram_ready() const { return d_[cur_].fhist >= 0; }
 
   // raw buffers (cur = current generation)
   void* rows(int which) { return rows_[which ^ cur_].ptr; }
-  float* scores(int which) { return (float*)scores_[which ^ cur_].ptr; }
-  unsigned long long* best_parts() { return (unsigned long long*)best_[cur_].ptr; }
-  uint32_t n_best() const { return n_best_[cur_]; }
-  void set_n_best(uint32_t n) {
-    n_best_[cur_] = n;
-    stats_ok_[cur_] = false;
-  }
+  float* scores(int which) { return scores_at(which ^ cur_); }
+  unsigned long long* best_parts() { return best_at(cur_); }
+  uint32_t n_best() const { return d_[cur_].n_best; }
+  void set_n_best(uint32_t n);
   size_t row_bytes() const { return 4ull * row_words_; }
 
   // scratch buffers for callers (migration staging)
@@ -230,11 +252,71 @@ class Island {
   void copy_to_device(void* dst, const void* src, size_t bytes);
 
  private:
+  // What is known about the population of parity p beyond rows_[p] and
+  // scores_[p]: by-products of the kernel that last wrote scores_[p].  Only
+  // the transitions below write it; scores_written() replaces the whole record
+  // of p by what that kernel delivered (`made`, everything else: nothing).
+  //
+  //   event (parity)               n_best  stats  part  qk   fhist   rank_cnt
+  //   scores_written(p, made):
+  //     initialize, evaluate       grid    (a)    -     -    -       -
+  //     jit_eval, rebest           grid    -      -     -    -       -
+  //     immigrate: stripe, GPU     grid    (a)    -     -    -       -
+  //                fused bottom-k  grid    -      -     -    -       -
+  //     run_plain (next)           grid    (a)    (b)   (c)  (d)     (e)
+  //     fused_jit_generation       grid    yes    -     -    -       -
+  //     run_batched (next)         grid    (a)    -     (c)  -       -
+  //     run_tiny: current / other  1 / 0   (a)/-  -     -    -       -
+  //   keys_requantized (cur)       .       .      .     yes  .       .
+  //   take_rank_counts (both)      .       .      .     .    .       -
+  //   drop_key_counts (both)       .       .      .     .    -       -
+  //   config_changed               = drop_key_counts, ++version_
+  //   set_n_best(n) (cur)          n       -      -     .    .       .
+  //   ("-": dropped, ".": kept)
+  //   (a) the kernel was given stats_parts_[p] (fused_stats())
+  //   (b) the report's partition, when (a) and its grid is the best-partials
+  //       count (the roulette prefix's carries)
+  //   (c) the REAL GEN kernel was given, and so wrote, quantized keys
+  //   (d) only on the launcher's report that its kernel took GenArgs::key_hist,
+  //       not on fhist_ready_for's prediction: fhist_[fhist_rot_ % 3].  It and
+  //       the next buffer z, which the launch zeroed, become clean, the other
+  //       parity loses a claim on z, the rotation advances.
+  //   (e) on the launcher's report; rank_ws_ is ONE buffer, so the other
+  //       parity loses its claim
+  // drop_key_counts also precedes a staged / init / eval launch() on the
+  // current rows and a graph replay (which produce neither).  qk_age_,
+  // fhist_clean_ / fhist_rot_ and the graph freshness (g_*) are not in here.
+  struct Derived {
+    uint32_t n_best = 0;        // valid entries of best_[p]
+    bool stats = false;         // stats_parts_[p] ({min, sum} per block) belongs to them
+    TpPartition part{0, 0, 0};  // the binary_gen_tp launch that stored stats_parts_[p] (grid 0: another kernel)
+    bool qk = false;            // keys_[p] holds the quantized keys of scores_[p] (REAL, see qk_ws_)
+    int fhist = -1;             // the fhist_ buffer with the histogram of its keys (-1: none)
+    bool rank_cnt = false;      // rank_ws_ holds the tile counts of its keys
+  } d_[2];
+  void scores_written(int p, const Derived& made);  // a kernel rewrote scores_[p]
+  void keys_requantized() { d_[cur_].qk = true; }   // prepare_generation() re-keyed the current scores
+  bool take_rank_counts();  // the current keys' tile counts are there; the sort that asks consumes them
+  void drop_key_counts();   // the launches that follow produce no histogram and no rank counts
+  void config_changed() { ++version_, drop_key_counts(); }
+  uint32_t tp_tail_ = 0;  // tail units of the last GEN launch (its report), not a fact about a parity
+
+  float* scores_at(int p) const { return scores_[p].as<float>(); }
+  unsigned long long* best_at(int p) const { return best_[p].as<unsigned long long>(); }
+  uint16_t* keys_at(int p) const { return keys_[p].as<uint16_t>(); }
+  float* stats_at(int p) const { return stats_parts_[p].as<float>(); }
+  // the integer objectives' exact u16 keys of parity p (nullptr: f32 scores)
+  uint16_t* int_keys_at(int p) const { return integer_objective(cfg_.objective, cfg_.L) ? keys_at(p) : nullptr; }
+
+  RngKey key() const;
   GenArgs make_args(int mode);
-  uint32_t launch(int mode, const GenArgs& a, unsigned long long* parts);
+  LsArgs ls_args(int kind, uint32_t moves, float prob) const;
+  LaunchReport launch(int mode, const GenArgs& a, unsigned long long* parts);
+  void evaluate_current(int mode);  // initialize() / evaluate(): MODE_INIT / MODE_EVAL on the current parity
   void prepare_generation();  // elitism indices, roulette prefix
-  Buffer alloc(size_t bytes);
-  void release(Buffer& b);
+  // grow-only b.reserve() on this island's backend; sync: the stream may
+  // still use the memory it frees
+  bool reserve(Buffer& b, size_t bytes, bool sync = false);
   void rebuild_mut_table();
   void ensure_topk_ws(uint32_t k);
 
@@ -244,12 +326,11 @@ class Island {
   int cur_ = 0;
   uint32_t gen_ = 0, epoch_ = 0;
   Buffer rows_[2], scores_[2], best_[2], keys_[2];
-  uint32_t n_best_[2] = {0, 0};
   Buffer mut_thr_, obj_data_[2], elite_idx_, cumfit_, cum_ws_, topk_ws_, stats_, out_best_, scratch_;
   Buffer rank_order_, rank_ws_;
   Buffer roul_guide_;  // roulette guide table (GPU), S + 1 entries
   // REAL on the GPU: quantized u16 tournament keys in keys_[p] (qkey), valid
-  // when qk_valid_[p]: written by the GEN kernel that bred parity p, or by
+  // when d_[p].qk: written by the GEN kernel that bred parity p, or by
   // prepare_generation() after anything else rewrote its scores.  qk_ws_ =
   // {min, max, sum, count} (+ score_stats workspace) of the scores of the
   // generation of the last refresh (every 8 or 32 generations, qk_age_), NOT
@@ -258,17 +339,19 @@ class Island {
   // All keys of ONE parity share a range; the two parities' ranges differ
   // across a refresh (only keys of one parity are ever compared).
   bool real_qk() const;
-  void invalidate_qk() {
-    qk_valid_[cur_] = false;
-    fhist_of_[cur_] = -1;  // the keys of the current population change
-    if (rank_cnt_of_ == cur_) rank_cnt_of_ = -1;
-  }
   Buffer qk_ws_;
-  bool qk_valid_[2] = {false, false};
   Buffer qubo_qt_;               // QUBO: int8 Q^T packed from objective data slot 0 (GPU)
   Buffer qubo_qn_;               // QUBO: int8 Q in the same padding (one-flip local search, GPU)
   uint32_t obj_version_ = 0, qubo_version_ = ~0u;
-  void prepare_objective();      // derived objective data (QUBO packing)
+  // derived objective data, each rebuilt once per data version
+  void prepare_objective() {
+    prepare_knapsack();
+    prepare_tsp_matrix();
+    prepare_qubo();
+  }
+  void prepare_knapsack();    // BINARY knapsack: the matrix-core digit table
+  void prepare_tsp_matrix();  // PERMUTATION TSP: the LDS-resident matrix
+  void prepare_qubo();        // QUBO: the packed int8 matrices (throws when Q is not set)
   // slot 0 as an L x L matrix is bitwise symmetric (checked once per data version, both backends)
   bool matrix_symmetric();
   void one_flip_search(uint32_t moves, float prob);  // local_search() of BINARY / OBJ_QUBO
@@ -279,18 +362,8 @@ class Island {
   Buffer knap_tab_;               // BINARY knapsack: matrix-core digit table (GPU, integer instances)
   uint32_t knap_version_ = ~0u, knap_dig_ = 0, knap_cols_ = 0;
   // fused statistics partials per parity ({min, sum} per block of the kernel
-  // that wrote best_[p]); stats_ok_[p]: they belong to the current best_[p]
+  // that wrote best_[p]), current when d_[p].stats
   Buffer stats_parts_[2];
-  bool stats_ok_[2] = {false, false};
-  // stats_part_[p]: the block partition of the binary_gen_tp launch whose
-  // partials stats_parts_[p] holds (grid 0: another kernel wrote them)
-  TpPartition stats_part_[2] = {{0, 0, 0}, {0, 0, 0}};
-  uint32_t tp_tail_ = 0;
-  void set_stats_ok(int p, bool ok) {
-    stats_ok_[p] = ok;
-    stats_part_[p] = TpPartition{0, 0, 0};
-  }
-  static bool roul_fused_off();  // PGA_ROUL_FUSED=0: the three-launch roulette prefix (A/B knob)
   bool fused_stats() const;  // the evaluating kernels of this configuration store them
   void append_history();
   Buffer hist_;
@@ -320,25 +393,18 @@ class Island {
   bool run_graph(uint32_t reps, bool fresh);
   bool capture_graph();
   void drop_graph();
-  void invalidate() {
-    ++version_;
-    fhist_of_[0] = fhist_of_[1] = -1;
-    rank_cnt_of_ = -1;
-  }
   // fused key histograms: three buffers of fused_hist_words(L + 1) words
   // rotated by the generations that produce one (each zeroes the next);
-  // fhist_of_[p] = the buffer with the histogram of parity p's population
+  // d_[p].fhist = the buffer with the histogram of parity p's population
   Buffer fhist_[3];
-  int fhist_of_[2] = {-1, -1};
   bool fhist_clean_[3] = {true, true, true};  // its selection status words are still zero
   uint32_t fhist_rot_ = 0;
   bool fhist_on_ = false, fhist_user_ = false;
-  bool fhist_ready_for(const GenArgs& a) const;  // this GEN launch produces the histogram
+  bool fhist_ready_for(const GenArgs& a);  // this GEN launch produces the histogram (allocates the buffers)
   // rank selection of an integer objective: the GEN kernel also stores the
-  // next rank sort's tile counts into rank_ws_ (GenArgs::rank_counts);
-  // rank_cnt_of_ = the parity whose keys they count (-1: none), consumed by
-  // the next prepare_generation's sort
-  int rank_cnt_of_ = -1;
+  // next rank sort's tile counts into rank_ws_ (GenArgs::rank_counts) for the
+  // parity it writes (d_[p].rank_cnt), consumed by the next
+  // prepare_generation's sort
   uint32_t* rank_counts_for_gen() const;
   const TopkFused* fused_select(TopkFused& f);    // the current population's histogram for a select
   uint32_t graph_g_ = 0, version_ = 0;

@@ -74,27 +74,28 @@ bool force_generic_kernels();
 
 // ---- encodings: one launch per call, returns the grid used (= number of
 // valid entries written to best_parts, when the mode evaluates) ----
-uint32_t binary_launch(int mode, const GenArgs& a, unsigned long long* best_parts, hipStream_t s);
-// binary_launch for one group size GS (binary_gs.hip, one translation unit per GS)
-template <int GS>
-uint32_t binary_launch_group(int mode, const GenArgs& a, unsigned long long* best_parts, hipStream_t s);
-// whether the last binary_launch on this host thread handed GenArgs::key_hist
-// to its kernel (so the fused key histogram was written and hist_zero
-// cleared); the island marks a histogram valid only on this report
-bool& binary_hist_written();
-// the same report for GenArgs::rank_counts (the next rank sort's tile counts)
-bool& binary_rank_counts_written();
-// the block partition of the last binary_gen_tp launch on this host thread
-// (grid 0: the launch took another kernel): block j wrote children
-// tp_share(S, unit, j, skew) and stored their {min, sum} partials at
-// stats_parts[2 j] (no pair pool)
+// the block partition of a binary_gen_tp launch (grid 0: the launch took
+// another kernel): block j wrote children tp_share(S, unit, j, skew) and
+// stored their {min, sum} partials at stats_parts[2 j] (no pair pool)
 // tail: the tail units the launch asked for (GenArgs::tp_tail after the LDS
 // clamp; 0: a kernel without tail steps, or none fit)
 struct TpPartition {
   uint32_t grid, unit, skew;
   uint32_t tail = 0;
 };
-TpPartition& binary_tp_partition();
+// what a launch did: its grid, whether its kernel was handed GenArgs::key_hist
+// (so the fused key histogram was written and hist_zero cleared; the island
+// marks a histogram valid only on this report) and GenArgs::rank_counts (the
+// next rank sort's tile counts), and its two-phase partition
+struct LaunchReport {
+  uint32_t grid = 0;
+  bool hist = false, rank_counts = false;
+  TpPartition part{0, 0, 0};
+};
+LaunchReport binary_launch(int mode, const GenArgs& a, unsigned long long* best_parts, hipStream_t s);
+// binary_launch for one group size GS (binary_gs.hip, one translation unit per GS)
+template <int GS>
+LaunchReport binary_launch_group(int mode, const GenArgs& a, unsigned long long* best_parts, hipStream_t s);
 // whether a MODE_GEN launch of these arguments takes the hot two-phase kernel
 // (binary_gen_tp) and which variant: group size, full groups, dense mutation.
 // For f32-score objectives (the fused JIT generation kernel, jit.hpp).
@@ -115,10 +116,11 @@ uint32_t perm_max_batch();
 uint32_t perm_launch_batch(const GenArgs* args, unsigned long long* const* parts, uint32_t n, hipStream_t s);
 // batched islands (binary_batch.hip): one MODE_GEN launch of up to
 // binary_max_batch() same-shape islands (args[i], best partials parts[i]);
-// returns each island's grid (its best-partials count), 0 when the islands do
-// not qualify (nothing launched: run them one by one)
+// reports each island's grid (its best-partials count; 0 when the islands do
+// not qualify, nothing launched: run them one by one) and the partition
+// (skew 0) with its tail; no histogram and no rank counts
 uint32_t binary_max_batch();
-uint32_t binary_launch_batch(const GenArgs* args, unsigned long long* const* parts, uint32_t n, hipStream_t s);
+LaunchReport binary_launch_batch(const GenArgs* args, unsigned long long* const* parts, uint32_t n, hipStream_t s);
 // Knapsack digit table for the matrix-core evaluation (binary.hip): false
 // (table empty) when the instance does not qualify -- non-integer values or
 // weights, sums of magnitudes >= 2^24, fewer than 4 lanes per individual, or
@@ -155,7 +157,9 @@ void qubo_ls_launch(const LsArgs& a, hipStream_t s);
 uint32_t qubo_eval_launch(const void* rows, uint32_t row_words, uint64_t S, uint32_t L, const int8_t* qt, float sign,
                           float* scores, unsigned long long* parts, hipStream_t s);
 
-inline uint32_t encoding_launch(int mode, const GenArgs& a, unsigned long long* best_parts, hipStream_t s) {
+// (the other encodings report their grid alone)
+inline LaunchReport encoding_launch(int mode, const GenArgs& a, unsigned long long* best_parts, hipStream_t s) {
+  LaunchReport r;
   switch (a.encoding) {
     case ENC_BINARY:
       if (a.objective == OBJ_QUBO && (mode == MODE_GEN || mode == MODE_INIT || mode == MODE_EVAL)) {
@@ -163,14 +167,16 @@ inline uint32_t encoding_launch(int mode, const GenArgs& a, unsigned long long* 
         GenArgs b = a;
         b.objective = OBJ_NONE;
         b.key_next = nullptr;
-        if (mode != MODE_EVAL) binary_launch(mode, b, best_parts, s);
-        return qubo_eval_launch(a.next, a.row_words, a.S, a.L, a.qubo_qt, a.obj_f0, a.score_next, best_parts, s);
+        if (mode != MODE_EVAL) r = binary_launch(mode, b, best_parts, s);
+        r.grid = qubo_eval_launch(a.next, a.row_words, a.S, a.L, a.qubo_qt, a.obj_f0, a.score_next, best_parts, s);
+        return r;
       }
       return binary_launch(mode, a, best_parts, s);
     case ENC_REAL:
-      if (a.user_xo_fn || a.user_mut_fn) return compat_launch(mode, a, best_parts, s);
-      return real_launch(mode, a, best_parts, s);
-    default: return perm_launch(mode, a, best_parts, s);
+      r.grid = (a.user_xo_fn || a.user_mut_fn) ? compat_launch(mode, a, best_parts, s)
+                                               : real_launch(mode, a, best_parts, s);
+      return r;
+    default: r.grid = perm_launch(mode, a, best_parts, s); return r;
   }
 }
 

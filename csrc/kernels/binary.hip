@@ -94,37 +94,19 @@ bool binary_tp_plan(const GenArgs& a, uint32_t& gs, bool& full, bool& dense) {
   return a.chunks <= 64u && fast && o32 && a.n_elite <= kTpMaxElite;
 }
 
-bool& binary_hist_written() {
-  static thread_local bool w = false;
-  return w;
-}
-
-bool& binary_rank_counts_written() {
-  static thread_local bool w = false;
-  return w;
-}
-
-TpPartition& binary_tp_partition() {
-  static thread_local TpPartition p{0, 0, 0};
-  return p;
-}
-
-uint32_t binary_launch(int mode, const GenArgs& a, unsigned long long* best_parts, hipStream_t s) {
-  uint32_t grid = 0;
-  binary_hist_written() = false;  // go_tp sets it when its kernel takes the histogram
-  binary_rank_counts_written() = false;
-  binary_tp_partition() = TpPartition{0, 0, 0};
+LaunchReport binary_launch(int mode, const GenArgs& a, unsigned long long* best_parts, hipStream_t s) {
+  LaunchReport r;
   switch (group_size(a.chunks)) {  // one translation unit per group size (binary_gs.hip)
-    case 1: grid = binary_launch_group<1>(mode, a, best_parts, s); break;
-    case 2: grid = binary_launch_group<2>(mode, a, best_parts, s); break;
-    case 4: grid = binary_launch_group<4>(mode, a, best_parts, s); break;
-    case 8: grid = binary_launch_group<8>(mode, a, best_parts, s); break;
-    case 16: grid = binary_launch_group<16>(mode, a, best_parts, s); break;
-    case 32: grid = binary_launch_group<32>(mode, a, best_parts, s); break;
-    default: grid = binary_launch_group<64>(mode, a, best_parts, s); break;
+    case 1: r = binary_launch_group<1>(mode, a, best_parts, s); break;
+    case 2: r = binary_launch_group<2>(mode, a, best_parts, s); break;
+    case 4: r = binary_launch_group<4>(mode, a, best_parts, s); break;
+    case 8: r = binary_launch_group<8>(mode, a, best_parts, s); break;
+    case 16: r = binary_launch_group<16>(mode, a, best_parts, s); break;
+    case 32: r = binary_launch_group<32>(mode, a, best_parts, s); break;
+    default: r = binary_launch_group<64>(mode, a, best_parts, s); break;
   }
   PGA_HIP_CHECK(hipGetLastError());
-  return grid;
+  return r;
 }
 
 }  // namespace pga

@@ -16,7 +16,7 @@ namespace pga {
 namespace {
 
 template <int GS, int OBJ>
-uint32_t batch_go(GenBatch& b, uint32_t n, uint64_t S, bool full, bool dense, hipStream_t s) {
+LaunchReport batch_go(GenBatch& b, uint32_t n, uint64_t S, bool full, bool dense, hipStream_t s) {
   const void* k = full ? (dense ? (const void*)binary_gen_tp_batch<GS, OBJ, true, true>
                                 : (const void*)binary_gen_tp_batch<GS, OBJ, true, false>)
                        : (dense ? (const void*)binary_gen_tp_batch<GS, OBJ, false, true>
@@ -44,12 +44,11 @@ uint32_t batch_go(GenBatch& b, uint32_t n, uint64_t S, bool full, bool dense, hi
     else hipLaunchKernelGGL((binary_gen_tp_batch<GS, OBJ, false, false>), grid, t.block, lds, s, b);
   }
   PGA_HIP_CHECK(hipGetLastError());
-  binary_tp_partition() = TpPartition{t.grid, t.unit, 0, tail};  // (every island of the batch)
-  return t.grid;
+  return LaunchReport{t.grid, false, false, TpPartition{t.grid, t.unit, 0, tail}};  // (every island of the batch)
 }
 
 template <int GS>
-uint32_t batch_obj(int obj, GenBatch& b, uint32_t n, uint64_t S, bool full, bool dense, hipStream_t s) {
+LaunchReport batch_obj(int obj, GenBatch& b, uint32_t n, uint64_t S, bool full, bool dense, hipStream_t s) {
   switch (obj) {
     case OBJ_ONEMAX: return batch_go<GS, OBJ_ONEMAX>(b, n, S, full, dense, s);
     case OBJ_LEADING_ONES: return batch_go<GS, OBJ_LEADING_ONES>(b, n, S, full, dense, s);
@@ -61,10 +60,10 @@ uint32_t batch_obj(int obj, GenBatch& b, uint32_t n, uint64_t S, bool full, bool
 
 uint32_t binary_max_batch() { return kMaxBatch; }
 
-uint32_t binary_launch_batch(const GenArgs* args, unsigned long long* const* parts, uint32_t n, hipStream_t s) {
-  if (n == 0 || n > kMaxBatch) return 0;
+LaunchReport binary_launch_batch(const GenArgs* args, unsigned long long* const* parts, uint32_t n, hipStream_t s) {
+  if (n == 0 || n > kMaxBatch) return {};
   const GenArgs& a0 = args[0];
-  if (a0.objective != OBJ_ONEMAX && a0.objective != OBJ_LEADING_ONES && a0.objective != OBJ_TRAP) return 0;
+  if (a0.objective != OBJ_ONEMAX && a0.objective != OBJ_LEADING_ONES && a0.objective != OBJ_TRAP) return {};
   uint32_t gs = 0;
   bool full = false, dense = false;
   GenBatch b;
@@ -75,13 +74,13 @@ uint32_t binary_launch_batch(const GenArgs* args, unsigned long long* const* par
     // every island: the hot kernel's conditions, the same variant, shape and objective
     if (!binary_tp_plan(a, g2, f2, d2) || a.key_cur == nullptr || a.S != a0.S || a.chunks != a0.chunks ||
         a.objective != a0.objective)
-      return 0;
+      return {};
     if (i == 0) {
       gs = g2;
       full = f2;
       dense = d2;
     } else if (g2 != gs || f2 != full || d2 != dense) {
-      return 0;
+      return {};
     }
     b.a[i] = a;
     b.parts[i] = parts[i];

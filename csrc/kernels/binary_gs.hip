@@ -22,14 +22,15 @@ namespace {
 using namespace dev;
 
 template <typename K>
-uint32_t go(K kernel, const GenArgs& a, unsigned long long* parts, uint32_t gpb, hipStream_t s) {
-  const uint32_t grid = launch_grid_occ(a.S, gpb, (const void*)kernel);
-  hipLaunchKernelGGL(kernel, grid, kBlock, 0, s, a, parts);
-  return grid;
+LaunchReport go(K kernel, const GenArgs& a, unsigned long long* parts, uint32_t gpb, hipStream_t s) {
+  LaunchReport r;
+  r.grid = launch_grid_occ(a.S, gpb, (const void*)kernel);
+  hipLaunchKernelGGL(kernel, r.grid, kBlock, 0, s, a, parts);
+  return r;
 }
 
 template <typename K>
-uint32_t go_tp(K kernel, const GenArgs& a0, unsigned long long* parts, hipStream_t s) {
+LaunchReport go_tp(K kernel, const GenArgs& a0, unsigned long long* parts, hipStream_t s) {
   const TpGeom t = tp_geometry(a0.S, 1, (const void*)kernel, 64 / group_size(a0.chunks));
   GenArgs a = a0;
   a.tp_unit = t.unit;
@@ -55,14 +56,12 @@ uint32_t go_tp(K kernel, const GenArgs& a0, unsigned long long* parts, hipStream
   a.tp_tail = key_obj ? tp_tail_units(t, group_size(a.chunks), lds, allow_dynamic_lds((const void*)kernel)) : 0u;
   if (a.tp_tail > 0) lds = tp_tail_off(lds) + a.tp_tail * kTpTailUnitBytes;
   hipLaunchKernelGGL(kernel, t.grid, t.block, lds, s, a, parts);
-  binary_hist_written() = hist;
-  binary_rank_counts_written() = rk;
-  binary_tp_partition() = TpPartition{t.grid, tp_unit(a, 64u / group_size(a.chunks)), a.tp_skew, a.tp_tail};
-  return t.grid;
+  return LaunchReport{t.grid, hist, rk,
+                      TpPartition{t.grid, tp_unit(a, 64u / group_size(a.chunks)), a.tp_skew, a.tp_tail}};
 }
 
 template <int GS, int OBJ>
-uint32_t launch_mode(int mode, const GenArgs& a, unsigned long long* parts, hipStream_t s) {
+LaunchReport launch_mode(int mode, const GenArgs& a, unsigned long long* parts, hipStream_t s) {
   constexpr uint32_t gpb = kBlock / GS;
   switch (mode) {
     case MODE_GEN: {
@@ -110,7 +109,7 @@ uint32_t launch_mode(int mode, const GenArgs& a, unsigned long long* parts, hipS
 }
 
 template <int GS>
-uint32_t launch_obj(int mode, const GenArgs& a, unsigned long long* parts, hipStream_t s) {
+LaunchReport launch_obj(int mode, const GenArgs& a, unsigned long long* parts, hipStream_t s) {
   switch (a.objective) {
     case OBJ_ONEMAX: return launch_mode<GS, OBJ_ONEMAX>(mode, a, parts, s);
     case OBJ_KNAPSACK: return launch_mode<GS, OBJ_KNAPSACK>(mode, a, parts, s);
@@ -123,7 +122,7 @@ uint32_t launch_obj(int mode, const GenArgs& a, unsigned long long* parts, hipSt
 }  // namespace
 
 template <>
-uint32_t binary_launch_group<PGA_BIN_GS>(int mode, const GenArgs& a, unsigned long long* best_parts, hipStream_t s) {
+LaunchReport binary_launch_group<PGA_BIN_GS>(int mode, const GenArgs& a, unsigned long long* best_parts, hipStream_t s) {
   return launch_obj<PGA_BIN_GS>(mode, a, best_parts, s);
 }
 
