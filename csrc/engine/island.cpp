@@ -641,6 +641,7 @@ void Island::run_plain(uint32_t n) {
       if (a.rank_counts) a.hist_bins = cfg_.L + 1;
       const LaunchReport rep = launch(MODE_GEN, a, best_at(nx));
       tp_tail_ = rep.part.tail;
+      route_ = rep.route;
       Derived made{rep.grid};
       made.stats = a.stats_parts != nullptr;
       // (the roulette prefix's carries, roulette_fused_launch)
@@ -724,7 +725,7 @@ bool Island::run_batched(const std::vector<Island*>& isls, uint32_t n, hipStream
     LaunchReport rep;  // (REAL and PERMUTATION report their grid alone)
     if (bin) rep = binary_launch_batch(args.data(), parts.data(), (uint32_t)N, s);
     else rep.grid = real ? real_launch_batch(args.data(), parts.data(), (uint32_t)N, s)
-                         : perm_launch_batch(args.data(), parts.data(), (uint32_t)N, s);
+                         : perm_launch_batch(args.data(), parts.data(), (uint32_t)N, s, &rep.route);
     if (rep.grid == 0) {
       if (g == 0) return false;  // not eligible (decided on the first generation's arguments)
       throw std::logic_error("batched islands stopped qualifying mid-run");
@@ -737,6 +738,7 @@ bool Island::run_batched(const std::vector<Island*>& isls, uint32_t n, hipStream
       made.qk = real && args[k].qk != nullptr;  // the REAL kernel writes the keys it is given
       I.scores_written(I.cur_ ^ 1, made);
       I.tp_tail_ = rep.part.tail;
+      I.route_ = rep.route;
       I.swap();
     }
   }

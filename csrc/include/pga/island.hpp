@@ -184,6 +184,10 @@ class Island {
   // keeps no such keys or those of that parity are not valid.  Launches
   // nothing and changes no state (the refresh age included).
   bool qkeys_host(int which, std::vector<uint16_t>& keys, float range[2]);
+  // read-only record of the kernel the last PERMUTATION generation took on
+  // the GPU (tests; ops.hpp PermRoute): kernel PERM_K_NONE before the first
+  // generation, on the CPU backend and for the other encodings
+  const PermRoute& route() const { return route_; }
 
   // ---- device-side building blocks (no sync) ----
   // idx_out: device (or host for CPU) memory.  sorted: best first (ties by
@@ -312,6 +316,7 @@ class Island {
   GenArgs make_args(int mode);
   LsArgs ls_args(int kind, uint32_t moves, float prob) const;
   LaunchReport launch(int mode, const GenArgs& a, unsigned long long* parts);
+  PermRoute route_;  // of the last MODE_GEN launch (route())
   void evaluate_current(int mode);  // initialize() / evaluate(): MODE_INIT / MODE_EVAL on the current parity
   void prepare_generation();  // elitism indices, roulette prefix
   // grow-only b.reserve() on this island's backend; sync: the stream may

@@ -83,14 +83,24 @@ struct TpPartition {
   uint32_t grid, unit, skew;
   uint32_t tail = 0;
 };
+// which PERMUTATION kernel a MODE_GEN launch took (perm.hip's launchers fill
+// it as they choose; host-only, for tests: Island::route).  kernel 0: none yet.
+// tbl: GenArgs::obj_aux_kind of the matrix table in LDS (0: the L2 matrix or
+// coordinates); unit: GenArgs::tp_unit (0: the generic and long kernels)
+enum PermKernel : uint32_t { PERM_K_NONE = 0, PERM_K_GENERIC = 1, PERM_K_FAST = 2, PERM_K_LONG = 3, PERM_K_BATCH = 4 };
+struct PermRoute {
+  uint32_t kernel = PERM_K_NONE, gs = 0, full = 0, tbl = 0, block = 0, unit = 0, grid = 0;
+};
 // what a launch did: its grid, whether its kernel was handed GenArgs::key_hist
 // (so the fused key histogram was written and hist_zero cleared; the island
 // marks a histogram valid only on this report) and GenArgs::rank_counts (the
-// next rank sort's tile counts), and its two-phase partition
+// next rank sort's tile counts), its two-phase partition, and the route of a
+// PERMUTATION generation
 struct LaunchReport {
   uint32_t grid = 0;
   bool hist = false, rank_counts = false;
   TpPartition part{0, 0, 0};
+  PermRoute route;
 };
 LaunchReport binary_launch(int mode, const GenArgs& a, unsigned long long* best_parts, hipStream_t s);
 // binary_launch for one group size GS (binary_gs.hip, one translation unit per GS)
@@ -113,7 +123,8 @@ uint32_t real_launch_batch(const GenArgs* args, unsigned long long* const* parts
 // PERMUTATION batched islands (perm.hip perm_gen_fast_batch): TSP objectives,
 // genomes of at most 512 cities
 uint32_t perm_max_batch();
-uint32_t perm_launch_batch(const GenArgs* args, unsigned long long* const* parts, uint32_t n, hipStream_t s);
+uint32_t perm_launch_batch(const GenArgs* args, unsigned long long* const* parts, uint32_t n, hipStream_t s,
+                           PermRoute* route = nullptr);
 // batched islands (binary_batch.hip): one MODE_GEN launch of up to
 // binary_max_batch() same-shape islands (args[i], best partials parts[i]);
 // reports each island's grid (its best-partials count; 0 when the islands do
@@ -135,7 +146,8 @@ uint32_t real_launch(int mode, const GenArgs& a, unsigned long long* best_parts,
 // operators, rotation, quantized keys; PGA_TINY_MULTI=0 turns it off)
 bool real_launch_multi(const GenArgs& a, unsigned long long* const parts[2], float* const stats[2], uint32_t n,
                        hipStream_t s);
-uint32_t perm_launch(int mode, const GenArgs& a, unsigned long long* best_parts, hipStream_t s);
+uint32_t perm_launch(int mode, const GenArgs& a, unsigned long long* best_parts, hipStream_t s,
+                     PermRoute* route = nullptr);
 // 2-opt local search stage (perm_ls.hip): one wave per tour, in place; genomes
 // of at most kPermMaxL cities (longer: std::invalid_argument "too long")
 void perm_ls_launch(const LsArgs& a, hipStream_t s);
@@ -176,7 +188,7 @@ inline LaunchReport encoding_launch(int mode, const GenArgs& a, unsigned long lo
       r.grid = (a.user_xo_fn || a.user_mut_fn) ? compat_launch(mode, a, best_parts, s)
                                                : real_launch(mode, a, best_parts, s);
       return r;
-    default: r.grid = perm_launch(mode, a, best_parts, s); return r;
+    default: r.grid = perm_launch(mode, a, best_parts, s, &r.route); return r;
   }
 }
 

@@ -10,7 +10,8 @@
 namespace pga {
 
 // longest genome of the 4-individuals-per-block kernels (their LDS arrays);
-// longer ones run one individual per 64-lane block (perm.hip go_long)
+// longer ones run one individual per 64-lane block (perm.hip go_long), and so
+// do the few below it whose arrays no longer fit beside Euclidean coordinates
 constexpr uint32_t kPermMaxL = 4096;
 
 // child-word layout extension for permutations

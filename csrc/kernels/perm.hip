@@ -37,6 +37,15 @@ inline uint32_t perm_max_length(bool euc) {  // longest genome the one-individua
   return (uint32_t)((160 * 1024 - 4 * kHdrF - 64 /* static LDS */) / (euc ? 16 : 8)) / 8 * 8;
 }
 
+// the route of the launch in progress (ops.hpp PermRoute): the MODE_GEN
+// launchers below record their choice here, perm_launch / perm_launch_batch
+// hand it to their caller
+thread_local PermRoute t_route;
+inline void note_route(uint32_t kernel, uint32_t gs, bool full, uint32_t tbl, uint32_t block, uint32_t unit,
+                       uint32_t grid) {
+  t_route = PermRoute{kernel, gs, full ? 1u : 0u, tbl, block, unit, grid};
+}
+
 __host__ __device__ inline size_t perm_lds_bytes(uint32_t GS, uint32_t chunks, bool euc, uint32_t blk = 256) {
   const uint32_t gpb = blk / GS;
   const size_t lp = 8ull * chunks;  // genes per padded row
@@ -768,6 +777,7 @@ uint32_t go_long(const GenArgs& a, unsigned long long* parts, hipStream_t s) {
   if (cap > kMaxGrid) cap = kMaxGrid;
   const uint32_t grid = (uint32_t)(a.S < cap ? a.S : cap);
   hipLaunchKernelGGL(k, grid, 64, lds, s, a, parts);
+  if (MODE == MODE_GEN) note_route(PERM_K_LONG, 64, false, 0, 64, 0, grid);
   return grid;
 }
 
@@ -776,7 +786,11 @@ uint32_t go(const GenArgs& a, unsigned long long* parts, hipStream_t s) {
   if (GS == 64 && a.L > kPermMaxL) return go_long<MODE, OBJ>(a, parts, s);
   const size_t lds = perm_lds_bytes(GS, a.chunks, OBJ == OBJ_TSP_EUC);
   auto k = perm_kernel<GS, MODE, OBJ>;
-  (void)allow_dynamic_lds((const void*)k);
+  const size_t avail = allow_dynamic_lds((const void*)k);
+  // four individuals' arrays and the EUC coordinates (576 + 320 bytes per
+  // chunk) stop fitting together near 4080 cities: one individual per block
+  // then too (the same kernel body, so the same children and sums)
+  if (GS == 64 && lds > avail) return go_long<MODE, OBJ>(a, parts, s);
   const uint32_t gpb = kBlock / GS;
   const uint64_t need = (a.S + gpb - 1) / gpb;
   int per_cu = 0;
@@ -786,6 +800,7 @@ uint32_t go(const GenArgs& a, unsigned long long* parts, hipStream_t s) {
   if (cap > kMaxGrid) cap = kMaxGrid;
   const uint32_t grid = (uint32_t)(need < cap ? need : cap);
   hipLaunchKernelGGL(k, grid, kBlock, lds, s, a, parts);
+  if (MODE == MODE_GEN) note_route(PERM_K_GENERIC, GS, false, 0, kBlock, 0, grid);
   return grid;
 }
 
@@ -827,6 +842,7 @@ uint32_t go_fast_blk(const GenArgs& a0, unsigned long long* parts, hipStream_t s
   const uint64_t need = ((a.S + a.tp_unit - 1) / a.tp_unit + nw - 1) / nw;
   const uint32_t grid = (uint32_t)(need < cap ? need : cap);
   hipLaunchKernelGGL(k, grid, blk, lds, s, a, parts);
+  note_route(PERM_K_FAST, GS, FULL, TBL, blk, a.tp_unit, grid);
   return grid;
 }
 
@@ -907,6 +923,7 @@ uint32_t batch_go(PermBatch& b, uint32_t n, hipStream_t s) {
   const uint32_t gx = (uint32_t)(need < cap ? need : cap);
   hipLaunchKernelGGL((perm_gen_fast_batch<GS, OBJ, TBL>), dim3(gx, n), kBlock, lds, s, b);
   PGA_HIP_CHECK(hipGetLastError());
+  note_route(PERM_K_BATCH, GS, false, TBL, kBlock, u, gx);
   return gx;
 }
 
@@ -942,7 +959,7 @@ uint32_t batch_obj(PermBatch& b, uint32_t n, hipStream_t s) {
 
 uint32_t perm_max_batch() { return kPermMaxBatch; }
 
-uint32_t perm_launch_batch(const GenArgs* args, unsigned long long* const* parts, uint32_t n, hipStream_t s) {
+static uint32_t perm_launch_batch_go(const GenArgs* args, unsigned long long* const* parts, uint32_t n, hipStream_t s) {
   if (n == 0 || n > kPermMaxBatch || force_generic_kernels()) return 0;
   const GenArgs& a0 = args[0];
   if (a0.objective != OBJ_TSP && a0.objective != OBJ_TSP_OPEN && a0.objective != OBJ_TSP_EUC) return 0;
@@ -966,9 +983,18 @@ uint32_t perm_launch_batch(const GenArgs* args, unsigned long long* const* parts
   }
 }
 
-uint32_t perm_launch(int mode, const GenArgs& a, unsigned long long* best_parts, hipStream_t s) {
+uint32_t perm_launch_batch(const GenArgs* args, unsigned long long* const* parts, uint32_t n, hipStream_t s,
+                           PermRoute* route) {
+  t_route = PermRoute{};
+  const uint32_t gx = perm_launch_batch_go(args, parts, n, s);
+  if (route && gx) *route = t_route;
+  return gx;
+}
+
+uint32_t perm_launch(int mode, const GenArgs& a, unsigned long long* best_parts, hipStream_t s, PermRoute* route) {
   if (a.L > 65535) throw std::invalid_argument("PERMUTATION encoding supports at most 65535 genes (u16 city ids)");
   uint32_t grid = 0;
+  t_route = PermRoute{};
   switch (group_size(a.chunks)) {
     case 1: grid = launch_obj<1>(mode, a, best_parts, s); break;
     case 2: grid = launch_obj<2>(mode, a, best_parts, s); break;
@@ -979,6 +1005,7 @@ uint32_t perm_launch(int mode, const GenArgs& a, unsigned long long* best_parts,
     default: grid = launch_obj<64>(mode, a, best_parts, s); break;
   }
   PGA_HIP_CHECK(hipGetLastError());
+  if (route) *route = t_route;
   return grid;
 }
 

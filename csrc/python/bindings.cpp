@@ -291,6 +291,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              return py::make_tuple(keys, range);
            },
            py::arg("which") = 0)
+      // the kernel the last PERMUTATION generation took on the GPU, or None
+      // (Island::route; read-only, tests)
+      .def("route",
+           [](const Island& i) -> py::object {
+             const pga::PermRoute& r = i.route();
+             if (r.kernel == pga::PERM_K_NONE) return py::none();
+             static const char* const names[] = {"", "generic", "fast", "long", "batch"};
+             py::dict d;
+             d["kernel"] = names[r.kernel];
+             d["GS"] = r.gs;
+             d["full"] = r.full != 0;
+             d["tbl"] = r.tbl;
+             d["block"] = r.block;
+             d["unit"] = r.unit;
+             d["grid"] = r.grid;
+             return d;
+           })
       .def("best_parts",
            [](const IslandPtr& i) { return view(i, i->best_parts(), {(int64_t)pga::kMaxGrid}, torch::kInt64); })
       .def_property("n_best", &Island::n_best, &Island::set_n_best)
