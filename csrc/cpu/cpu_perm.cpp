@@ -144,9 +144,10 @@ uint32_t perm_run(int mode, const GenArgs& a, unsigned long long* best_parts) {
   return 1;
 }
 
-// 2-opt local search stage (perm_ops.hpp two_opt_*), mirror of perm_ls.hip:
-// the same pairs, gains and tie-break, the same edge-length bookkeeping and
-// the score of MODE_EVAL above for every row that moved
+// 2-opt / Or-opt local search stage (perm_ops.hpp two_opt_* / or_opt_*, by
+// LsArgs::kind), mirror of perm_ls.hip: the same candidates, gains and
+// tie-break, the same edge lengths after every move and the score of MODE_EVAL
+// above for every row that moved
 void perm_local_search(const LsArgs& a) {
   const uint32_t L = a.L, nch = a.chunks, GS = group_size(nch);
   const uint64_t rh = 2ull * a.row_words;  // u16 per row
@@ -157,14 +158,66 @@ void perm_local_search(const LsArgs& a) {
     w = std::min(w, L - 1);
     return euc ? tsp_euc_dist(a.obj_data, u, w) : a.obj_data[(size_t)u * L + w];
   };
+  // Or-opt (perm_ops.hpp or_opt_*): the first strict maximum in (p, q, s, r)
+  // loop order, whatever the length; the tour is rebuilt and every edge length
+  // recomputed after a move
+  const auto or_opt_move = [&](uint16_t* t, std::vector<float>& el, std::vector<uint16_t>& tmp) -> bool {
+    float bg = 0.f;  // a NaN gain never passes the strict >
+    uint32_t bp = 0, bq = 0, bs = 0, br = 0;
+    for (uint32_t p = 0; p < L; ++p) {
+      const uint32_t pm = p ? p - 1 : L - 1, smax = or_opt_smax(p, L);
+      // per segment length s = k + 1: d(a, b), the segment's own edges forwards and backwards
+      float dab[3] = {0.f, 0.f, 0.f}, fwd[3] = {0.f, 0.f, 0.f}, rev[3] = {0.f, 0.f, 0.f};
+      for (uint32_t s = 1; s <= smax; ++s) {
+        dab[s - 1] = (open && (p == 0 || p + s == L)) ? 0.f : dist(t[pm], t[(p + s) % L]);
+        if (s == 2) fwd[1] = el[p], rev[1] = dist(t[p + 1], t[p]);
+        if (s == 3) fwd[2] = fwd[1] + el[p + 1], rev[2] = rev[1] + dist(t[p + 2], t[p + 1]);
+      }
+      for (uint32_t q = 0; q < L; ++q) {
+        const uint32_t c = t[q], e = t[(q + 1) % L];
+        const bool closing = open && q == L - 1;
+        for (uint32_t s = 1; s <= smax; ++s) {
+          if (!or_opt_q_ok(p, s, q, L)) continue;
+          const uint32_t x = t[p], y = t[p + s - 1];
+          const float removed = or_opt_removed(el[pm], el[p + s - 1], el[q]);
+          for (uint32_t r = 0; r < (s >= 2 ? 2u : 1u); ++r) {
+            const float g = r == 0 ? or_opt_gain(removed, dab[s - 1], dist(c, x), closing ? 0.f : dist(y, e))
+                                   : or_opt_gain_rev(removed, fwd[s - 1], dab[s - 1], dist(c, y),
+                                                     closing ? 0.f : dist(x, e), rev[s - 1]);
+            if (g > bg) {
+              bg = g;
+              bp = p, bq = q, bs = s, br = r;
+            }
+          }
+        }
+      }
+    }
+    if (!(bg > 0.f)) return false;
+    // the tour without the segment, the segment behind the city that was t[q]
+    tmp.clear();
+    for (uint32_t k = 0; k < L; ++k) {
+      if (k < bp || k >= bp + bs) tmp.push_back(t[k]);
+      if (k == bq)
+        for (uint32_t i = 0; i < bs; ++i) tmp.push_back(t[br ? bp + bs - 1 - i : bp + i]);
+    }
+    std::copy(tmp.begin(), tmp.end(), t);
+    for (uint32_t k = 0; k < L; ++k) el[k] = (open && k == L - 1) ? 0.f : dist(t[k], t[(k + 1) % L]);
+    return true;
+  };
   parallel_for(a.S, 16, [&](uint64_t n_begin, uint64_t n_end, unsigned) {
     std::vector<float> el(L);
+    std::vector<uint16_t> tmp;
     for (uint64_t n = n_begin; n < n_end; ++n) {
       if (!ls_selected(a, n)) continue;
       uint16_t* t = rows + n * rh;
       for (uint32_t p = 0; p < L; ++p) el[p] = (open && p == L - 1) ? 0.f : dist(t[p], t[(p + 1) % L]);
       bool moved = false;
       for (uint32_t m = 0; m < a.moves; ++m) {
+        if (a.kind == LS_OR_OPT) {
+          if (!or_opt_move(t, el, tmp)) break;
+          moved = true;
+          continue;
+        }
         float bg = 0.f;  // the first maximum in (i, j) order; a NaN gain never passes the strict >
         uint32_t bp = 0;
         for (uint32_t i = 0; i + 2 < L; ++i) {

@@ -44,6 +44,7 @@ bool roul_fused_off() {  // PGA_ROUL_FUSED=0: the three-launch roulette prefix
   return off;
 }
 const char kJitNotTwoOpt[] = "2-opt local search needs a built-in TSP objective, not a JIT objective";
+const char kJitNotOrOpt[] = "Or-opt local search needs a built-in TSP objective, not a JIT objective";
 const char kJitNotOneFlip[] = "one-flip local search needs the built-in QUBO objective, not a JIT objective";
 }  // namespace
 
@@ -192,7 +193,8 @@ void Island::set_operators(const Config& c) {
   if (c.selection < SEL_TOURNAMENT || c.selection > SEL_RANK) throw std::invalid_argument("unknown selection");
   if (c.selection == SEL_RANK && !(c.rank_pressure >= 1.f && c.rank_pressure <= 2.f))
     throw std::invalid_argument("rank pressure must be in [1, 2]");
-  if (c.local_search != LS_NONE && c.local_search != LS_TWO_OPT && c.local_search != LS_ONE_FLIP)
+  if (c.local_search != LS_NONE && c.local_search != LS_TWO_OPT && c.local_search != LS_ONE_FLIP &&
+      c.local_search != LS_OR_OPT)
     throw std::invalid_argument("unknown local search");
   if (c.local_search == LS_ONE_FLIP && (c.encoding != ENC_BINARY || c.objective != OBJ_QUBO))
     throw std::invalid_argument("one-flip local search needs the BINARY encoding with the built-in QUBO objective");
@@ -200,6 +202,11 @@ void Island::set_operators(const Config& c) {
     if (c.encoding != ENC_PERMUTATION) throw std::invalid_argument("2-opt local search needs the PERMUTATION encoding");
     if (c.objective != OBJ_TSP && c.objective != OBJ_TSP_OPEN && c.objective != OBJ_TSP_EUC)
       throw std::invalid_argument("2-opt local search needs a built-in TSP objective");
+  }
+  if (c.local_search == LS_OR_OPT) {
+    if (c.encoding != ENC_PERMUTATION) throw std::invalid_argument("Or-opt local search needs the PERMUTATION encoding");
+    if (c.objective != OBJ_TSP && c.objective != OBJ_TSP_OPEN && c.objective != OBJ_TSP_EUC)
+      throw std::invalid_argument("Or-opt local search needs a built-in TSP objective");
   }
   const float old_rate = cfg_.mut_rate;
   const int32_t old_mut = cfg_.mutation;
@@ -352,22 +359,36 @@ bool Island::matrix_symmetric() {
 }
 
 void Island::local_search(uint32_t moves, float prob) {
+  // the configured kind; without one, the stage of the population: one-flip
+  // for BINARY with the QUBO objective, 2-opt otherwise
+  int kind = cfg_.local_search;
+  if (kind == LS_NONE) kind = (cfg_.encoding == ENC_BINARY && cfg_.objective == OBJ_QUBO) ? LS_ONE_FLIP : LS_TWO_OPT;
+  local_search(moves, prob, kind);
+}
+
+void Island::local_search(uint32_t moves, float prob, int kind) {
   TraceRange tr("pga.local_search");
-  if (cfg_.encoding == ENC_BINARY && cfg_.objective == OBJ_QUBO && cfg_.local_search != LS_TWO_OPT) {
+  if (kind != LS_TWO_OPT && kind != LS_ONE_FLIP && kind != LS_OR_OPT) throw std::invalid_argument("unknown local search");
+  if (kind == LS_ONE_FLIP) {
+    if (cfg_.encoding != ENC_BINARY || cfg_.objective != OBJ_QUBO)
+      throw std::invalid_argument("one-flip local search needs the BINARY encoding with the built-in QUBO objective");
     one_flip_search(moves, prob);
     return;
   }
+  const bool oro = kind == LS_OR_OPT;
+  const std::string name = oro ? "Or-opt" : "2-opt";
   if (cfg_.encoding != ENC_PERMUTATION)
-    throw std::invalid_argument("2-opt local search needs the PERMUTATION encoding (one-flip: BINARY with the QUBO objective)");
-  if (jit_) throw std::invalid_argument(kJitNotTwoOpt);
+    throw std::invalid_argument(name + " local search needs the PERMUTATION encoding (one-flip: BINARY with the QUBO objective)");
+  if (jit_) throw std::invalid_argument(oro ? kJitNotOrOpt : kJitNotTwoOpt);
   const bool euc = cfg_.objective == OBJ_TSP_EUC;
   if (!euc && cfg_.objective != OBJ_TSP && cfg_.objective != OBJ_TSP_OPEN)
-    throw std::invalid_argument("2-opt local search needs a built-in TSP objective");
+    throw std::invalid_argument(name + " local search needs a built-in TSP objective");
   if (obj_len_[0] < (euc ? 2ull * cfg_.L : (size_t)cfg_.L * cfg_.L))
-    throw std::invalid_argument("2-opt local search: the objective data is not set");
-  if (!euc && !matrix_symmetric())
+    throw std::invalid_argument(name + " local search: the objective data is not set");
+  // Or-opt turns no edge outside its own segment round: any matrix will do
+  if (!oro && !euc && !matrix_symmetric())
     throw std::invalid_argument("2-opt local search needs a symmetric distance matrix");
-  LsArgs a = ls_args(LS_TWO_OPT, moves, prob);
+  LsArgs a = ls_args(kind, moves, prob);
   prepare_objective();
   if (!euc && aux_kind_ && aux_on_) {
     a.obj_aux = obj_aux_.ptr;
@@ -578,7 +599,10 @@ void Island::prepare_generation() {
 void Island::run(uint32_t n) {
   TraceRange tr("pga.run");
   if (cfg_.local_search != LS_NONE) {  // a stage follows every generation: plain launches only
-    if (jit_) throw std::invalid_argument(cfg_.local_search == LS_ONE_FLIP ? kJitNotOneFlip : kJitNotTwoOpt);
+    if (jit_)
+      throw std::invalid_argument(cfg_.local_search == LS_ONE_FLIP ? kJitNotOneFlip
+                                  : cfg_.local_search == LS_OR_OPT ? kJitNotOrOpt
+                                                                   : kJitNotTwoOpt);
     run_plain(n);
     return;
   }

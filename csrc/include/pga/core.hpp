@@ -95,6 +95,7 @@ enum LocalSearch : int32_t {
   LS_NONE = 0,
   LS_TWO_OPT = 1,  // PERMUTATION, TSP objectives: best-improvement 2-opt moves (perm_ops.hpp)
   LS_ONE_FLIP = 2, // BINARY, OBJ_QUBO: best-improvement single-bit flips (qubo_ops.hpp)
+  LS_OR_OPT = 3,   // PERMUTATION, TSP objectives, any matrix: best-improvement segment moves (perm_ops.hpp)
 };
 
 enum MigrationPolicy : int32_t {
@@ -534,13 +535,13 @@ struct LsArgs {
   RngKey key;     // key.gen: the island's current generation counter
   int32_t objective;         // OBJ_TSP / OBJ_TSP_OPEN / OBJ_TSP_EUC, or OBJ_QUBO
   const float* obj_data;     // L*L distance matrix, L (x, y) coordinates, or the L*L matrix Q
-  const void* obj_aux;       // GenArgs::obj_aux (kinds 1 and 3), nullptr: the f32 matrix
+  const void* obj_aux;       // GenArgs::obj_aux (kinds 1 and 3; LS_OR_OPT: 2 as well), nullptr: the f32 matrix
   uint32_t obj_aux_kind, obj_aux_bytes;
   uint32_t moves;            // at most this many moves per selected individual
   uint32_t thresh, always;   // selected iff always or the ST_LS word < thresh
   // LS_ONE_FLIP (GPU): Q^T and Q as int8, padded to qubo_padded_length(L)
   // square (qt[n * Lp + k] = q[k][n], qn[n * Lp + k] = q[n][k]); the score
-  // factor Config::obj_f0; the stage's kind (LS_TWO_OPT / LS_ONE_FLIP)
+  // factor Config::obj_f0; the stage's kind (LS_TWO_OPT / LS_OR_OPT / LS_ONE_FLIP)
   const int8_t* qubo_qt;
   const int8_t* qubo_qn;
   float obj_f0;

@@ -28,7 +28,7 @@ uint32_t encoding_run(int mode, const GenArgs& a, unsigned long long* best_parts
 uint32_t binary_run(int mode, const GenArgs& a, unsigned long long* best_parts);
 uint32_t real_run(int mode, const GenArgs& a, unsigned long long* best_parts);
 uint32_t perm_run(int mode, const GenArgs& a, unsigned long long* best_parts);
-// 2-opt local search stage, bit-identical to perm_ls.hip (any genome length)
+// 2-opt / Or-opt local search stage (LsArgs::kind), bit-identical to perm_ls.hip (any genome length)
 void perm_local_search(const LsArgs& a);
 // one-flip local search stage of OBJ_QUBO (qubo_ops.hpp), bit-identical to qubo_ls.hip
 void qubo_local_search(const LsArgs& a);

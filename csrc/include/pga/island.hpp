@@ -154,7 +154,12 @@ class Island {
   // TSP objective (matrix objectives: a symmetric matrix), no JIT objective.
   // BINARY with OBJ_QUBO runs the one-flip stage instead (qubo_ops.hpp): up to
   // `moves` best-improvement single-bit flips, the same selection rule.
+  // With Config::local_search = LS_OR_OPT the PERMUTATION stage is Or-opt
+  // (perm_ops.hpp or_opt_*): segments of 1 to 3 cities move, in either
+  // orientation; any matrix, symmetric or not.  The second form names the
+  // kind for this one stage, whatever the configuration says.
   void local_search(uint32_t moves, float prob);
+  void local_search(uint32_t moves, float prob, int kind);
 
   // ---- queries (synchronise the stream) ----
   unsigned long long best_packed();

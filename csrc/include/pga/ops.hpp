@@ -148,7 +148,7 @@ bool real_launch_multi(const GenArgs& a, unsigned long long* const parts[2], flo
                        hipStream_t s);
 uint32_t perm_launch(int mode, const GenArgs& a, unsigned long long* best_parts, hipStream_t s,
                      PermRoute* route = nullptr);
-// 2-opt local search stage (perm_ls.hip): one wave per tour, in place; genomes
+// 2-opt / Or-opt local search stage (perm_ls.hip, by LsArgs::kind): one wave per tour, in place; genomes
 // of at most kPermMaxL cities (longer: std::invalid_argument "too long")
 void perm_ls_launch(const LsArgs& a, hipStream_t s);
 

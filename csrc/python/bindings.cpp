@@ -58,7 +58,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   E(XO_UNIFORM); E(XO_ONE_POINT); E(XO_TWO_POINT); E(XO_BLEND); E(XO_ARITHMETIC); E(XO_PMX); E(XO_OX); E(XO_NONE);
   E(MUT_BIT_FLIP); E(MUT_GAUSSIAN); E(MUT_UNIFORM); E(MUT_RESET_ONE); E(MUT_SWAP); E(MUT_INVERSION); E(MUT_NONE);
   E(MIG_TOPK); E(MIG_STRIPE);
-  E(LS_NONE); E(LS_TWO_OPT); E(LS_ONE_FLIP);
+  E(LS_NONE); E(LS_TWO_OPT); E(LS_ONE_FLIP); E(LS_OR_OPT);
   E(OBJ_NONE); E(OBJ_ONEMAX); E(OBJ_KNAPSACK); E(OBJ_TRAP); E(OBJ_LEADING_ONES); E(OBJ_QUBO);
   E(OBJ_SPHERE); E(OBJ_RASTRIGIN); E(OBJ_ROSENBROCK); E(OBJ_ACKLEY); E(OBJ_GRIEWANK); E(OBJ_SCHWEFEL);
   E(OBJ_LINEAR); E(OBJ_KNAPSACK_REAL); E(OBJ_TSP_RANDOM_KEY); E(OBJ_TSP); E(OBJ_TSP_OPEN); E(OBJ_TSP_EUC); E(OBJ_USER_FNPTR);
@@ -238,11 +238,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("swap", &Island::swap)
       .def("rebest", [](Island& i) { bind_stream(i); i.rebest(); })
       .def("local_search",
-           [](Island& i, uint32_t moves, float prob) {
+           [](Island& i, uint32_t moves, float prob, int kind) {
              bind_stream(i);
-             i.local_search(moves, prob);
+             if (kind == pga::LS_NONE) i.local_search(moves, prob);  // the configured kind
+             else i.local_search(moves, prob, kind);
            },
-           py::arg("moves") = 1, py::arg("prob") = 1.f)
+           py::arg("moves") = 1, py::arg("prob") = 1.f, py::arg("kind") = (int)pga::LS_NONE)
       .def("best",
            [](Island& i) {
              bind_stream(i);

@@ -75,9 +75,17 @@ int pga_set_rank_pressure(pga_t *p, population_t *pop, float sp);
  * QUBO objective (PGA_OBJ_QUBO, Max-Cut included): each move flips the single
  * bit with the largest gain in score, ties to the lowest position, and a row
  * stops when no flip gains; Q need not be symmetric; exact integer arithmetic.
- * pga_local_search picks the stage by the population: 2-opt for PERMUTATION,
- * one-flip for BINARY with QUBO. */
-enum pga_local_search { PGA_LS_NONE = 0, PGA_LS_TWO_OPT = 1, PGA_LS_ONE_FLIP = 2 };
+ * PGA_LS_OR_OPT is the segment move for PERMUTATION with a TSP objective and
+ * ANY matrix, asymmetric ones included (2-opt's usual companion on symmetric
+ * ones): each move takes the 1 to 3 consecutive cities t[p .. p+s) (never
+ * across the array's end) out of the tour and puts them back between t[q] and
+ * t[q+1], as they were or reversed, whichever of all (p, s, q, orientation)
+ * gains most in f32; ties go to the smallest (p, q, s, orientation), and a row
+ * stops when nothing gains.  An open path (PGA_OBJ_TSP_OPEN) is a closed tour
+ * whose closing edge has length 0.
+ * pga_local_search runs the kind set here; with kind NONE it picks the stage
+ * by the population: 2-opt for PERMUTATION, one-flip for BINARY with QUBO. */
+enum pga_local_search { PGA_LS_NONE = 0, PGA_LS_TWO_OPT = 1, PGA_LS_ONE_FLIP = 2, PGA_LS_OR_OPT = 3 };
 int pga_set_local_search(pga_t *p, population_t *pop, enum pga_local_search kind, unsigned moves, float prob);
 int pga_local_search(pga_t *p, population_t *pop);
 

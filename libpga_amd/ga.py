@@ -34,7 +34,7 @@ MUTATIONS = {
 }
 
 LOCAL_SEARCHES = {None: C.LS_NONE, "none": C.LS_NONE, "two_opt": C.LS_TWO_OPT,
-                  "one_flip": C.LS_ONE_FLIP}
+                  "one_flip": C.LS_ONE_FLIP, "or_opt": C.LS_OR_OPT}
 
 
 def default_device() -> torch.device:
@@ -118,7 +118,7 @@ class GeneticAlgorithm:
         cfg.rank_pressure = float(ops.rank_pressure)
         cfg.n_elite = int(ops.elitism)
         if ops.local_search not in LOCAL_SEARCHES:
-            raise ValueError(f"unknown local search {ops.local_search!r} (None, 'two_opt' or 'one_flip')")
+            raise ValueError(f"unknown local search {ops.local_search!r} (None, 'two_opt', 'or_opt' or 'one_flip')")
         cfg.local_search = LOCAL_SEARCHES[ops.local_search]
         cfg.ls_moves = int(ops.ls_moves)
         cfg.ls_prob = float(ops.ls_prob)
@@ -164,12 +164,18 @@ class GeneticAlgorithm:
         else:
             self._island.evaluate()
 
-    def local_search(self, moves: Optional[int] = None, prob: Optional[float] = None) -> None:
+    def local_search(self, moves: Optional[int] = None, prob: Optional[float] = None,
+                     kind: Optional[str] = None) -> None:
         """One local search stage on the current population, in place: up to
         ``moves`` best-improvement moves on each individual selected with
         probability ``prob`` (defaults: the operators' ``ls_moves`` /
-        ``ls_prob``).  PERMUTATION with a native TSP objective (a symmetric
-        matrix, or coordinates): 2-opt moves.  BINARY with the native QUBO
+        ``ls_prob``).  ``kind`` names the stage for this call ("two_opt",
+        "or_opt", "one_flip"); None runs the operators' ``local_search``, or
+        without one the stage of the population.  PERMUTATION with a native
+        TSP objective: 2-opt moves (a symmetric matrix, or coordinates), or
+        with "or_opt" segment moves -- 1 to 3 consecutive cities go elsewhere
+        in the tour, in either orientation -- on any matrix, asymmetric ones
+        and open paths (``TSP.reference_e3``) included.  BINARY with the native QUBO
         objective (``QUBO``, ``MaxCut``; Q need not be symmetric): single-bit
         flips, the largest gain first, ties to the lowest bit, in exact
         integer arithmetic.  No score gets worse; rows that moved are
@@ -183,7 +189,9 @@ class GeneticAlgorithm:
         p = self.operators.ls_prob if prob is None else prob
         if int(m) < 0:
             raise ValueError("moves must be >= 0")
-        self._island.local_search(int(m), float(p))
+        if kind is not None and (kind not in LOCAL_SEARCHES or LOCAL_SEARCHES[kind] == C.LS_NONE):
+            raise ValueError(f"unknown local search {kind!r} ('two_opt', 'or_opt' or 'one_flip')")
+        self._island.local_search(int(m), float(p), int(LOCAL_SEARCHES[kind]))
 
     def step(self) -> None:
         self.run(1)

@@ -35,8 +35,9 @@ class Operators:
     elitism: int = 0
     rank_pressure: float = 1.5  # selection="rank": linear ranking pressure in [1, 2]
     # local search stage after every generation (GeneticAlgorithm.local_search):
-    # None, "two_opt" (PERMUTATION, TSP) or "one_flip" (BINARY, QUBO / MaxCut),
-    # moves per selected individual, share selected
+    # None, "two_opt" (PERMUTATION, TSP with a symmetric matrix or coordinates),
+    # "or_opt" (PERMUTATION, TSP with any matrix) or "one_flip" (BINARY, QUBO /
+    # MaxCut), moves per selected individual, share selected
     local_search: Optional[str] = None
     ls_moves: int = 1
     ls_prob: float = 1.0
